@@ -14,6 +14,15 @@ timing is barrier + synchronize on both sides, max over ranks.  The metric's for
 (1M) per step, so an N-GPU step processes N x 1M strings and `value` is their sum over the
 max-over-ranks time; --scaling strong splits --global-batch strings (1M) of a step over
 the ranks instead.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs:
+it sets up, warms up, times the K steps of the host entry and prints the result line.
+--dump-outputs DIR also writes the last timed step's result as DIR/<name>.npy (dump_outputs).
+--full adds everything else the line can carry, each in runs of its own after the headline:
+the oracle comparisons (checked_vs_oracle), the kernel-resident rate and its roofline, the
+varied batch, the lazy engine, the f64-cell and fractional-weight legs and the CPU baseline.
+The switches that shape those legs (--no-e2e, --no-varied, --lazy-batch, --no-f64, --no-cpu,
+--cpu-seconds, --cpu-threads) act under --full only.
 """
 import argparse
 import ctypes as C
@@ -164,7 +173,19 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget")
     p.add_argument("--cpu-threads", type=int, default=0, help="0 = nproc (the affinity mask)")
     p.add_argument("--no-cpu", action="store_true")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run everything else the line reports: oracle "
+                        "comparisons, kernel-resident rate + roofline, varied batch, lazy "
+                        "engine, f64-cell / fractional-weight legs, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the result of the last timed step of the host entry (rank 0's "
+                        "shard) as DIR/<name>.npy, at most 64 MB in all")
+    args = p.parse_args()
+    if not args.e2e and not args.full:
+        p.error("--no-e2e replaces the headline by the kernel-resident leg: it needs --full")
+    if not args.e2e and args.dump_outputs:
+        p.error("--dump-outputs writes the host entry's result: not with --no-e2e")
+    return args
 
 
 def dev_ptr(t):
@@ -445,6 +466,47 @@ def check_host_result(r, labels, offsets, blob_bytes, sem, n=256):
     return int(n)
 
 
+DUMP_STRINGS = 1 << 20   # per-string arrays: whole up to this many strings (8 MB each as f64)
+DUMP_PATHS = 1 << 14     # per-arc arrays: the paths of at most this many strings ...
+DUMP_ARCS = 1 << 20      # ... cut at this many arcs (3 x 8 MB as f64)
+
+
+def dump_outputs(r, out_dir):
+    """--dump-outputs: the host BatchResult of the last timed step as out_dir/<name>.npy, in
+    float64 (every u32 label and every offset is exact in it; status in float32), 53 MB at
+    the most.  Up to DUMP_STRINGS strings the per-string arrays (status, offsets, finals)
+    are whole; of a larger batch they hold a sorted sample of half as many strings, drawn
+    with a fixed seed (`strings`; each one's path begins at `offsets_begin` and ends at
+    `offsets`).  The per-arc arrays (ilabels, olabels, weights) hold the whole paths of a
+    fixed-seed sample of DUMP_PATHS strings (`path_strings`), concatenated in string order
+    and cut at DUMP_ARCS arcs.  Both samples depend on the batch size alone, so two builds
+    dump the same strings."""
+    os.makedirs(out_dir, exist_ok=True)
+    num = len(r.status)
+    rng = np.random.default_rng(0xD0D0)
+    whole = num <= DUMP_STRINGS
+    strings = np.arange(num) if whole else np.sort(
+        rng.choice(num, DUMP_STRINGS // 2, replace=False))
+    paths = np.arange(num) if num <= DUMP_PATHS else np.sort(
+        rng.choice(num, DUMP_PATHS, replace=False))
+    offs = np.asarray(r.offsets).astype(np.int64)
+    status = np.asarray(r.status)[strings]
+    out = {"strings": strings, "path_strings": paths, "status": status.astype(np.float32),
+           "offsets": offs if whole else offs[strings + 1],
+           # a string without a path has no final weight: its slot is not part of the result
+           "finals": np.where(status == F.FST_PATH_OK, np.asarray(r.finals)[strings], 0.0)}
+    if not whole:
+        out["offsets_begin"] = offs[strings]
+    begin, count = offs[paths], offs[paths + 1] - offs[paths]
+    first = np.cumsum(count) - count            # each sampled path's place in the dump
+    arcs = (np.repeat(begin - first, count) + np.arange(int(count.sum())))[:DUMP_ARCS]
+    for name in ("ilabels", "olabels", "weights"):
+        out[name] = np.asarray(getattr(r, name))[arcs]
+    for name, a in out.items():
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -522,45 +584,55 @@ def main():
     # ---- headline: the host entry, host arrays in and out (SURVEY 8(d) wall time) ----
     h_labels = np.ones(args.batch * L, np.uint32)          # the caller's (pageable) arrays
     h_offsets = np.arange(args.batch + 1, dtype=np.uint64) * L
+    checked = None
     if args.e2e:
         el, hkms, res = host_timed(rhs, sem, local, h_labels, h_offsets, args.steps,
                                    args.warmup, world)
         assert np.all(res.status == F.FST_PATH_OK), np.unique(res.status, return_counts=True)
         assert int(res.offsets[-1]) == args.batch * L
-        checked = check_host_result(res, h_labels, h_offsets, blob_check, sem)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(res, args.dump_outputs)
+        if args.full:
+            checked = check_host_result(res, h_labels, h_offsets, blob_check, sem)
         del res
 
-    # ---- kernel-only: the same strings device-resident (fst_device_compose_shortest_path) --
-    batch = DeviceBatch(lengths, lambda t: torch.ones(t, dtype=torch.int32), dev)
-    kel, kms, st = timed(batch, rhs, sem, local, args.steps, args.warmup, world)
-    status = batch.status.cpu().numpy()
-    plen = batch.plen.cpu().numpy().astype(np.int64)
-    assert np.all(status == F.FST_PATH_OK), np.unique(status, return_counts=True)
-    assert np.all(plen == L)
-    kchecked = check_sample(batch, blob_check, sem)
-    # one untimed run with the per-string work counters (B_alg of the roofline)
-    batch.run(rhs, sem, local, torch.cuda.current_stream().cuda_stream, work=True)
-    torch.cuda.synchronize()
-    work = batch.work.cpu().numpy().astype(np.int64)
-    avg_k = float(np.mean(kms))
-    balg = b_alg_bytes(work, lengths, plen)   # bytes per launch on this rank
-    if not args.e2e:  # (profiling runs) the headline falls back to the kernel-resident rate
-        el, hkms, checked = kel, kms, kchecked
+    if not args.full:  # a plain run: the headline alone, none of the legs below
+        args.varied, args.lazy_batch, args.f64, args.no_cpu = False, 0, False, True
+    extra = {}
+    batch = None
+    if args.full:
+        # ---- kernel-only: the same strings device-resident (fst_device_compose_shortest_path)
+        batch = DeviceBatch(lengths, lambda t: torch.ones(t, dtype=torch.int32), dev)
+        kel, kms, st = timed(batch, rhs, sem, local, args.steps, args.warmup, world)
+        status = batch.status.cpu().numpy()
+        plen = batch.plen.cpu().numpy().astype(np.int64)
+        assert np.all(status == F.FST_PATH_OK), np.unique(status, return_counts=True)
+        assert np.all(plen == L)
+        kchecked = check_sample(batch, blob_check, sem)
+        # one untimed run with the per-string work counters (B_alg of the roofline)
+        batch.run(rhs, sem, local, torch.cuda.current_stream().cuda_stream, work=True)
+        torch.cuda.synchronize()
+        work = batch.work.cpu().numpy().astype(np.int64)
+        avg_k = float(np.mean(kms))
+        balg = b_alg_bytes(work, lengths, plen)   # bytes per launch on this rank
+        if not args.e2e:  # (profiling runs) the headline falls back to the kernel-resident rate
+            el, hkms, checked = kel, kms, kchecked
+        extra = {"value_kernel": total_per_step * args.steps / kel,
+                 "kernel_resident": {
+                     "value": total_per_step * args.steps / kel,
+                     "ms_per_step": kel / args.steps * 1e3, "kernel_ms": avg_k,
+                     "checked_vs_oracle": kchecked,
+                     "note": "fst_device_compose_shortest_path on device-resident labels/"
+                             "outputs: kernels only, no host copies (the roofline's kernel)"},
+                 "end_to_end": None if not args.e2e else {
+                     "ms_per_call": el / args.steps * 1e3,
+                     "kernel_ms_per_call": float(np.mean(hkms)),
+                     "bytes_in_per_call": int(h_labels.nbytes + h_offsets.nbytes),
+                     "note": "the headline: fst_compose_frozen_shortest_path_batch, pageable "
+                             "host labels in, pinned host result out (the streamed batch: "
+                             "labels staged into the result while the kernel reads them, "
+                             "paths copied out by the kernel)"}}
     value = total_per_step * args.steps / el
-    extra = {"value_kernel": total_per_step * args.steps / kel,
-             "kernel_resident": {
-                 "value": total_per_step * args.steps / kel,
-                 "ms_per_step": kel / args.steps * 1e3, "kernel_ms": avg_k,
-                 "checked_vs_oracle": kchecked,
-                 "note": "fst_device_compose_shortest_path on device-resident labels/outputs: "
-                         "kernels only, no host copies (the roofline's kernel)"},
-             "end_to_end": None if not args.e2e else {"ms_per_call": el / args.steps * 1e3,
-                            "kernel_ms_per_call": float(np.mean(hkms)),
-                            "bytes_in_per_call": int(h_labels.nbytes + h_offsets.nbytes),
-                            "note": "the headline: fst_compose_frozen_shortest_path_batch, "
-                                    "pageable host labels in, pinned host result out (the "
-                                    "streamed batch: labels staged into the result while the "
-                                    "kernel reads them, paths copied out by the kernel)"}}
 
     if args.varied:
         rng = np.random.default_rng(1234 + rank)
@@ -665,7 +737,8 @@ def main():
             "data": "synthetic (reference bench generators: 1^64 repeat acceptors, "
                     "ambiguous-chain rhs)",
             "timed": ("host entry: pageable host labels in -> kernels -> host result "
-                      "(SURVEY 8(d) wall time); kernel-only rate in value_kernel") if args.e2e
+                      "(SURVEY 8(d) wall time)" + ("; kernel-only rate in value_kernel"
+                                                   if args.full else "")) if args.e2e
                      else "kernel-resident only (--no-e2e profiling run)",
             "config": {"workload": "compose_frozen_shortest_path_ambiguous",
                        "semantics": args.semantics, "len": L,
@@ -677,11 +750,11 @@ def main():
                                         f"weak: {args.batch} strings per GPU per step"),
                        "parallelism": f"dp{world} (string shards, rhs replicated via "
                                       f"{'RCCL' if args.backend == 'nccl' else args.backend} broadcast)"},
-            "roofline": roofline_block(args, sem, avg_k, balg, work, lengths, plen, traffic,
-                                       traffic_src),
-            "cpu_baseline": cpu,
-            "checked_vs_oracle": checked,
         }
+        if args.full:
+            line.update({"roofline": roofline_block(args, sem, avg_k, balg, work, lengths, plen,
+                                                    traffic, traffic_src),
+                         "cpu_baseline": cpu, "checked_vs_oracle": checked})
         line.update(extra)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -8,7 +8,7 @@ for r in $(seq 1 "$rounds"); do
   for spec in "$@"; do
     name="${spec%%=*}"; lib="${spec#*=}"
     [ "$lib" = default ] && lib=""
-    LIBFST_AMD_LIB="$lib" timeout -k 10 150 python -u bench.py --no-cpu --no-e2e --no-varied \
+    LIBFST_AMD_LIB="$lib" timeout -k 10 150 python -u bench.py --full --no-cpu --no-e2e --no-varied \
       --no-f64 --steps 10 --warmup 2 > gpurun_out/ab_$name.$r.json 2> gpurun_out/ab_$name.$r.err
     rc=$?
     python3 - "$name" "$r" "$rc" <<'PY'

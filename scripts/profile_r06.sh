@@ -11,10 +11,10 @@ out=$1; shift
 mkdir -p "$out"
 export TMPDIR=/tmp
 C="--no-cpu --lazy-batch 0 --no-varied --no-e2e --no-f64"
-BE="bench.py --steps 20 --warmup 2 $C"
-BL="bench.py --semantics lazy --steps 20 --warmup 2 $C"
-SE="bench.py --steps 2 --warmup 1 $C --batch 65536"
-SL="bench.py --semantics lazy --steps 2 --warmup 1 $C --batch 65536"
+BE="bench.py --full --steps 20 --warmup 2 $C"
+BL="bench.py --full --semantics lazy --steps 20 --warmup 2 $C"
+SE="bench.py --full --steps 2 --warmup 1 $C --batch 65536"
+SL="bench.py --full --semantics lazy --steps 2 --warmup 1 $C --batch 65536"
 P1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS"
 P2="SQ_INSTS_SALU SQ_INSTS_SMEM SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_INSTS_BRANCH"
 R="rocprofv3 --output-format csv"

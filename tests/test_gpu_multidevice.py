@@ -229,7 +229,7 @@ def test_bench_two_ranks_one_gpu(mode):
                 "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port)]
     cmd = (launcher if mode == "strong" else [sys.executable]) + [
            os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--scaling", mode, "--global-batch", "8192", "--batch", "4096",
+           "--full", "--backend", "gloo", "--scaling", mode, "--global-batch", "8192", "--batch", "4096",
            "--no-cpu", "--no-varied", "--lazy-batch", "0", "--no-f64"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
