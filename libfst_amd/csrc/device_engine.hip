@@ -78,7 +78,14 @@ __global__ void build_mirror_kernel(const uint8_t* blob, uint32_t ns, uint32_t n
       const uint32_t a = pa[e.arc_offset].ilabel, z = pa[e.arc_offset + e.num_arcs - 1].ilabel;
       uint32_t na_ = 1;
       while (na_ < e.num_arcs && pa[e.arc_offset + na_].ilabel == a) ++na_;
-      two = make_uint4(a, z, na_, pa[e.arc_offset + na_].ilabel == z ? 1u : 0u);
+      // na_ == num_arcs: every arc carries the ilabel 0xFFFFFFFE, whose value is kSpanMixed
+      // (no second run to read).  Such a state keeps z = kSpanMixed and sspan2.w = 0, and
+      // every reader sends it through its search like any mixed state; a reader asked for
+      // the label 0xFFFFFFFE never trusts z == label (span_summary), since every mixed
+      // state would match.  A state whose arcs all carry 0xFFFFFFFF keeps z = kSpanNone:
+      // the whole span for that label (an arcless state: 0 arcs), nothing for any other.
+      const bool two_runs = na_ < e.num_arcs && pa[e.arc_offset + na_].ilabel == z;
+      two = make_uint4(a, z, na_, two_runs ? 1u : 0u);
       neps = a == 0u ? na_ : 0u;
     }
     sspan[ni] = make_uint4(e.arc_offset, e.num_arcs, uniq, neps);
@@ -217,6 +224,19 @@ static DeviceFst* finish_device(DeviceFst* d, const FrozenFst& f) {
   d->nan = f.has_nan_weight();
   d->finite = f.arc_weights_finite();
   d->weight_type = f.weight_type();
+  // band replay's slot fold: arcs in (ilabel, olabel) order within every state (the lazy
+  // pull's ol_ordered in eager_pull.hip asks the same of arcs into one target)
+  d->band_ol_sorted = true;
+  {
+    const PackedArc* pa = f.arcs();
+    for (uint32_t i = 0; i < ns && d->band_ol_sorted; ++i)
+      for (uint32_t a = se[i].arc_offset + 1; a < se[i].arc_offset + se[i].num_arcs; ++a)
+        if (pa[a].ilabel < pa[a - 1].ilabel ||
+            (pa[a].ilabel == pa[a - 1].ilabel && pa[a].olabel < pa[a - 1].olabel)) {
+          d->band_ol_sorted = false;
+          break;
+        }
+  }
   // band replay's strided arc table (<= 1 GB; without it the band reads spans first)
   if (d->has_eps && jb == 0 && max_span > 0 && max_span <= 64 && ns > 0 &&
       !std::getenv("FSTAMD_NO_BAND_TABLE")) {
@@ -1693,11 +1713,13 @@ hipError_t DeviceEngine::run_lazy_band(const DeviceFst& rhs, const ChainInput& i
   ws.sil = rhs.band_il;
   ws.srec = rhs.band_rec;
   ws.ssh = rhs.band_sh;
+  ws.olsort = rhs.band_ol_sorted ? 1u : 0u;
   if (std::getenv("FSTAMD_ROUTE_LOG"))
     for (const Plan& p : plans)
       std::fprintf(stderr, "[libfst_amd route] band plan: %u strings, lcap %u, grid %u of %u waves "
-                   "(budget %.1f GB), window %u states, arc table %s\n", p.count, p.lcap, p.grid,
-                   max_waves, budget / 1e9, p.wstates, ws.sil ? "on" : "off");
+                   "(budget %.1f GB), window %u states, arc table %s, slot fold %s\n", p.count,
+                   p.lcap, p.grid, max_waves, budget / 1e9, p.wstates, ws.sil ? "on" : "off",
+                   ws.olsort && rhs.view.jump_fwd < 32 ? "on" : "off");
   // the exact early exit needs every arc and final weight >= +0, finite
   // arcs; FSTAMD_NO_EARLY=1 replays the whole product as the reference does (tests, A/B)
   ws.early = (rhs.nonneg && rhs.finite && !std::getenv("FSTAMD_NO_EARLY")) ? 1u : 0u;
@@ -1714,7 +1736,9 @@ hipError_t DeviceEngine::run_lazy_band(const DeviceFst& rhs, const ChainInput& i
     HIP_TRY(hipMemsetAsync(ctr + 36, 0, 4, stream));
     // back pointers of 1, 2 or 4 B: one instance each
     // (and the slot path's preconditions as a compile-time fact when they hold)
-    const bool fp = ws.sil != nullptr && rhs.view.jump_fwd < 32;
+    // (the slot fold also needs the arcs in (ilabel, olabel) order: an rhs without it takes
+    // the label-comparing fold in the other instances)
+    const bool fp = ws.sil != nullptr && rhs.view.jump_fwd < 32 && rhs.band_ol_sorted;
     auto* kern = fp ? (bkb == 1 ? lazy_band_kernel<1, true> : bkb == 2 ? lazy_band_kernel<2, true>
                                                                          : lazy_band_kernel<4, true>)
                     : (bkb == 1 ? lazy_band_kernel<1, false> : bkb == 2 ? lazy_band_kernel<2, false>

@@ -168,6 +168,10 @@ struct DeviceFst {
   uint32_t* band_il = nullptr;
   ArcRec* band_rec = nullptr;
   uint32_t band_sh = 0;
+  // every state's arcs are non-decreasing in (ilabel, olabel) (fromMutable sorts them so; a
+  // fromBytes blob need only be ilabel-sorted): the band's slot fold needs it, since it
+  // breaks a tie between equal-distance arcs into one target by arc position
+  bool band_ol_sorted = false;
   // The device's state numbering (old id -> new id; empty = the blob's own ids): a
   // breadth-first renumbering of an rhs with scattered ids (device_engine.hip
   // bfs_renumbering).  Every device view (RhsView, RevView) uses it; results do not.

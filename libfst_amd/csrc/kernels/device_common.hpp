@@ -237,7 +237,10 @@ template <bool kTwo = false>
 __device__ __forceinline__ void span_summary(const RhsView& r, uint32_t s, uint32_t label,
                                              uint32_t& lo, uint32_t& cnt) {
   const uint4 ss = r.sspan[FB(s, r.num_states, 30)];
-  if (ss.z == label) {
+  // (the label 0xFFFFFFFE has kSpanMixed's value: it equals the summary word of every mixed
+  // state, so it always takes the search.  0xFFFFFFFF = kSpanNone needs no such care: a
+  // state without arcs answers it with its 0 arcs, a state of that one label with all.)
+  if (ss.z == label && label != kSpanMixed) {
     lo = ss.x;
     cnt = ss.y;
   } else if (ss.z != kSpanMixed) {

@@ -109,7 +109,7 @@ __device__ __forceinline__ CtSpans ct_spans_wave(const RhsView& rhs, const uint3
   bool need = false;
   if (sp.arc && sp.c != kEpsilon) {
     sp.lo = ss.x;
-    if (ss.z == sp.c) {
+    if (ss.z == sp.c && sp.c != kSpanMixed) {  // (a label with the marker's value: search)
       sp.cnt = ss.y;
     } else if (ss.z == kSpanMixed) {
       if (ss.y <= 8) {  // span_by_ilabel's independent loads

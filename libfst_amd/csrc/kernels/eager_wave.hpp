@@ -91,7 +91,7 @@ __device__ __forceinline__ bool wave_load_layer(const RhsView& rhs, uint32_t lab
 #pragma unroll
   for (int e = 0; e < EMAX; ++e) {
     uint32_t l = ss[e].x, c = ss[e].y;
-    if (ss[e].z != label) {
+    if (ss[e].z != label || label == kSpanMixed) {  // (a label with the marker's value: search)
       c = 0;
       if (ss[e].z == kSpanMixed) {
         uint32_t a0, b0;

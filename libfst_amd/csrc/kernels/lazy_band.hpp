@@ -73,6 +73,9 @@ struct LbWs {
   const uint32_t* sil;
   const ArcRec* srec;
   uint32_t ssh;
+  // 1: every state's arcs are in (ilabel, olabel) order (DeviceFst::band_ol_sorted), the
+  // slot path's third precondition; 0: every pop takes the label-comparing fold
+  uint32_t olsort;
 };
 
 // The id -> window index map of the newest kLbRing ids also lives in LDS (the rest: the
@@ -115,8 +118,8 @@ struct LbLds {
   };
 };
 
-// FP: the host guarantees the strided arc table and jump_fwd < 32 (the slot path's
-// preconditions), so neither is tested per pop
+// FP: the host guarantees the strided arc table, jump_fwd < 32 and arcs in (ilabel, olabel)
+// order (the slot path's preconditions), so none is tested per pop
 template <uint32_t BKB, bool FP>
 __device__ __forceinline__ void lazy_band_string(const RhsView& rhs, const ChainInput& in,
                                                  const LbWs& ws, const BatchOutDev& out,
@@ -138,7 +141,8 @@ __device__ __forceinline__ void lazy_band_string(const RhsView& rhs, const Chain
   constexpr uint32_t LS = RING - 64;
   const uint32_t S0 = rhs.start;  // every reachable state is >= S0 (arcs go forward)
   const uint32_t SCAP = ws.scap;
-  const bool jf32 = FP || rhs.jump_fwd < 32;  // a pop's targets fit 2 x 32 slots (the slot path)
+  // the slot path: a pop's targets fit 2 x 32 slots, and a tie goes to the lower arc position
+  const bool jf32 = FP || (ws.olsort != 0u && rhs.jump_fwd < 32);
   auto wix = [&](uint32_t k_, uint32_t s_) { return (s_ & wmask) * LC + k_; };  // x 2 + f
   // v / LC for window indices v < 2^26 (the host plan checks WS * LC < 2^26): one 64-bit
   // multiply instead of a ~35-instruction integer division, exact since 2^38 >= v * LC
@@ -889,13 +893,18 @@ lazy_band_kernel(RhsView rhs, ChainInput in, uint32_t n_best, unsigned int* next
     else if (L > ws.lcap)
       pre = kPathUnsupported;
     if (pre == kPathOk) {
+      // label 0: lhs epsilon phases.  Label 0xFFFFFFFF with the strided arc table: the
+      // table's padding slots carry that ilabel and a pop reads all 2^ssh slots of a state,
+      // so such a string would match them (phantom arcs into state 0); the rounds engine
+      // answers it, and the pop loop needs no arc count
+      const bool pad_label = ws.sil != nullptr;
       bool zero_label = false;
       for (uint32_t i = lane; i < L; i += 64) {
         const uint32_t x = in.labels[off + i];
         lab[i] = x;
-        zero_label |= x == kEpsilon;
+        zero_label |= x == kEpsilon || (pad_label && x == 0xFFFFFFFFu);
       }
-      if (__ballot(zero_label) != 0ull) pre = kPathUnsupported;  // lhs epsilon phases
+      if (__ballot(zero_label) != 0ull) pre = kPathUnsupported;
       wave_lds_sync();
     }
     pre = (int32_t)uni((uint32_t)pre);
