@@ -119,6 +119,12 @@ constexpr uint32_t kPullWtMax = 256;
 __host__ __device__ inline const double* rv_weight_table(const RevView& rv) {
   return reinterpret_cast<const double*>(rv.rrec4 + ((rv.nrec + 1u) & ~1u));
 }
+// tier P's packed-cell records (DeviceFst::pack; kernels/eager_pull.hpp): nrec words in that
+// same place -- an rhs has either the weight table (weights no scale makes integers) or
+// these (integer weights <= kRec8WMax), never both, and the view gains no field
+__host__ __device__ inline const uint32_t* rv_packed(const RevView& rv) {
+  return rv.rrec4 + ((rv.nrec + 1u) & ~1u);
+}
 constexpr double kRec8WMax = 7.0;
 
 struct DeviceFst {
@@ -147,6 +153,9 @@ struct DeviceFst {
                              // weight is an integer >= 0 below 2^24, else -1
   bool widx = false;         // rrec4 holds weight-table indices (RK 4 / 5; rv_weight_table)
   uint32_t wt_n = 0;         // distinct arc weights in that table (<= kPullWtMax)
+  // rrec4 is followed by the packed-cell records (rv_packed): integer weights <= kRec8WMax,
+  // a jump span of at most 63 states, no in-label 0xFFFFFF.  Per launch pull_pack decides
+  bool pack = false;
   // the direct layout with every in-arc group within 255 / kp blocks: a back record can be
   // one byte, the in-arc's position x * kp + m in its target's group (the chases re-derive
   // the record from the target state: tier P with rrec4, the lazy pull with any records)

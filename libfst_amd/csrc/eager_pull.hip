@@ -32,21 +32,33 @@ const void* pull_kernel_ptr(bool direct) {
 #ifndef FSTAMD_PULL_WAVES_F32  // A/B builds: the same with f32 cells (8-B cells, f32 merge)
 #define FSTAMD_PULL_WAVES_F32 6
 #endif
+// (RK 6, the packed cells: 7 waves as RK 3 -- see DESIGN.md §3.1 for the 7-against-8 A/B)
 // ... and with the 8-B records: 7 waves (3 VGPRs spilled outside the layer loop) measured
 // 37.1 ms per 1M metric strings, 6 waves 37.7 ms, 8 waves (10 spilled) 38.9 ms
 #ifndef FSTAMD_PULL_WAVES_R8
 #define FSTAMD_PULL_WAVES_R8 7
 #endif
+#ifndef FSTAMD_PULL_WAVES_PACK  // A/B builds: the same with packed cells (RK 6)
+#define FSTAMD_PULL_WAVES_PACK FSTAMD_PULL_WAVES_R8
+#endif
 template <int RK>
 const void* pull_kernel_for(const RevView& rv) {
   const bool dir = rv.direct != 0;
-  constexpr int wv = RK == 5 ? 4  // (f64 cells and a 2 KB weight table: 8.9 KB of LDS)
-                   : RK == 4 ? FSTAMD_PULL_WAVES_SMALL  // (f64 cells)
-                   : RK >= 2 ? FSTAMD_PULL_WAVES_R8 : RK ? FSTAMD_PULL_WAVES_F32 : FSTAMD_PULL_WAVES_SMALL;
-  switch (rv.kp) {
-    case 4: return pull_kernel_ptr<4, wv, RK>(dir);
-    case 5: return pull_kernel_ptr<5, wv, RK>(dir);
-    default: return pull_kernel_ptr<8, 4, RK>(dir);
+  if constexpr (RK == 6) {  // (the direct layout only: DeviceFst::pack)
+    switch (rv.kp) {
+      case 4: return (const void*)eager_pull_kernel<kPullRows, 4, true, FSTAMD_PULL_WAVES_PACK, 6>;
+      case 5: return (const void*)eager_pull_kernel<kPullRows, 5, true, FSTAMD_PULL_WAVES_PACK, 6>;
+      default: return (const void*)eager_pull_kernel<kPullRows, 8, true, 4, 6>;
+    }
+  } else {
+    constexpr int wv = RK == 5 ? 4  // (f64 cells and a 2 KB weight table: 8.9 KB of LDS)
+                     : RK == 4 ? FSTAMD_PULL_WAVES_SMALL  // (f64 cells)
+                     : RK >= 2 ? FSTAMD_PULL_WAVES_R8 : RK ? FSTAMD_PULL_WAVES_F32 : FSTAMD_PULL_WAVES_SMALL;
+    switch (rv.kp) {
+      case 4: return pull_kernel_ptr<4, wv, RK>(dir);
+      case 5: return pull_kernel_ptr<5, wv, RK>(dir);
+      default: return pull_kernel_ptr<8, 4, RK>(dir);
+    }
   }
 }
 // the 8-B records when the rhs has them (every weight an integer <= kRec8WMax)
@@ -69,8 +81,24 @@ int pull_rk(const DeviceFst& rhs, uint32_t max_len) {
   if (rhs.rev.rrec4 && use_rec8(rhs.rev) && !std::getenv("FSTAMD_NO_REC4")) return 3;
   return use_rec8(rhs.rev) ? 2 : 1;
 }
+// RK 3 with packed (distance, key) cells (RK 6 of the kernel; the log still says records 3):
+// the rhs has the packed records, and no distance field of the launch can wrap -- real
+// distances stay below 0x7F00, and an absent slot's, which starts there and may grow by a
+// weight per layer, below 2^16.  Strings longer than max_len are handed on by the kernel.
+// FSTAMD_NO_PACK=1: the unpacked RK 3 path (read per call)
+bool pull_pack(const DeviceFst& rhs, uint32_t max_len) {
+  return rhs.pack && pull_rk(rhs, max_len) == 3 &&
+         ((double)max_len + 1.0) * rhs.int_wmax < (double)0x7F00 && !std::getenv("FSTAMD_NO_PACK");
+}
 const void* pull_kernel_for(const DeviceFst& rhs, uint32_t max_len, bool log = false) {
-  switch (route_rk("eager", pull_rk(rhs, max_len), rhs.rev, log)) {
+  const int rk = route_rk("eager", pull_rk(rhs, max_len), rhs.rev, log);
+  if (rk == 3) {
+    const bool pack = pull_pack(rhs, max_len);
+    if (log && std::getenv("FSTAMD_ROUTE_LOG"))
+      std::fprintf(stderr, "[libfst_amd route] eager pull: packed cells %s\n", pack ? "on" : "off");
+    if (pack) return pull_kernel_for<6>(rhs.rev);
+  }
+  switch (rk) {
     case 0: return pull_kernel_for<0>(rhs.rev);
     case 5: return pull_kernel_for<5>(rhs.rev);
     case 4: return pull_kernel_for<4>(rhs.rev);
@@ -129,6 +157,7 @@ void free_reverse_mirror(DeviceFst* d) {
   d->pull_ok = false;
   d->widx = false;
   d->wt_n = 0;
+  d->pack = false;
 }
 
 bool build_reverse_mirror(DeviceFst* d, const FrozenFst& f) {
@@ -382,6 +411,31 @@ bool build_reverse_mirror(DeviceFst* d, const FrozenFst& f) {
     for (size_t r = 0; r < rrec.size(); ++r)  // the weight: an integer below 2^24
       rrec32[r] = make_uint4(rrec[r].src, rrec[r].y, wsc(rrec[r].weight), rolab[r]);
   }
+  // Packed-cell records (kernels/eager_pull.hpp, RK 6), appended to the 4-B ones: delta4 << 24
+  // | w << 16 | j << 4 | m with delta4 = 4 * (target - source - dlo) in one byte (a jump span
+  // of at most 63 states).  A padding slot repeats its block's first record with m = 15; a
+  // block without records holds 15, and the kernel reads it only under the label-miss
+  // shift or in masked lanes -- so no state may carry the in-label 0xFFFFFF, the row word
+  // of a state without in-arcs
+  bool pack = !rrec4.empty() && !widx && !rrec8.empty() && kp < 15 && rbias8 % 8 == 0;
+  for (size_t g = 0; g < groups.size() && pack; ++g) pack = groups[g].label != 0xFFFFFFu;
+  for (size_t r = 0; r < rrec4.size() && pack; ++r)
+    pack = rrec4[r] == 0xFFFF0000u || (rrec4[r] >> 16) / 2 <= 252;
+  if (pack) {
+    const size_t n = rrec4.size();
+    rrec4.resize(((n + 1) & ~(size_t)1) + n, 0xFFFF0000u);
+    uint32_t* const rpk = rrec4.data() + ((n + 1) & ~(size_t)1);
+    for (size_t r = 0; r < n; ++r) {
+      const uint32_t v = rrec4[r];
+      if (v == 0xFFFF0000u) {
+        const size_t first = r - r % kp;  // (a block's records fill its leading slots)
+        rpk[r] = first < r && rrec4[first] != 0xFFFF0000u ? (rpk[first] & ~15u) | 15u : 15u;
+      } else {
+        rpk[r] = ((v >> 17) << 24) | ((v & 0xFFu) << 16) | (((v >> 13) & 7u) << 4) | ((v >> 9) & 15u);
+      }
+    }
+  }
+  d->pack = pack;
   if (rrec4.empty()) wtab.clear();  // (the table serves the 4-B records only)
   if (!wtab.empty()) {  // appended to the records (rv_weight_table)
     d->wt_n = (uint32_t)wtab.size();

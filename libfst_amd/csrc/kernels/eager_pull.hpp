@@ -101,6 +101,46 @@ struct PullLds<W, true> {
   ChaseJob job[kChaseBatch];
 };
 
+// Packed cells (RK 6, a variant of RK 3 the host picks when the rhs and the launch fit it):
+// one u32 per slot, distance << 16 | rank << 7, so that a candidate
+//   cand = cell + (record & 0xFFFFFF) = (d + w) << 16 | rank << 7 | j << 4 | m
+// orders as (distance, source rank, arc position): ONE unsigned min per in-arc yields the
+// row's distance and its back key together (shortest-path.zig's tie rule is that
+// lexicographic minimum), and a 16-bit min of the low halves the first key.  No separate
+// distance min, no tight pass.  1.3 KB of cells instead of 2.6 KB.
+// A slot with no tuple holds kPackAbsent: its distance field sits above every real one
+// ((max_len + 1) * weight < 0x7F00 per launch, pull_pack in eager_pull.hip: the field of an
+// absent slot may grow by a weight per layer and still cannot wrap), its rank field is 511.
+// Records (rv_packed): delta4 << 24 | w << 16 | j << 4 | m with delta4 = 4 * (target -
+// source) + rbias8 / 2, the byte distance between the two cells.  Padding slots of a block
+// repeat the block's first record with m = 15 (same candidate, larger key: never the back
+// key, never a new first key); blocks without any record hold 15 and are read only by rows
+// under the label-miss shift or by lanes the hub loop masks.
+constexpr uint32_t kPackAbsent = 0x7F00FF80u;
+constexpr uint32_t kPackNoRank = 0xFF80u;  // low half of a candidate from an absent slot: >=
+constexpr uint32_t kPackPadM = 15u;
+template <int W>
+struct PullLdsPacked {
+  static constexpr int kWords = W * 8 / 64;
+  uint32_t cell[W + 1];            // distance << 16 | rank << 7 (kPackAbsent: no tuple)
+  unsigned long long bits[kWords];
+  uint4 pre[kWords];
+  unsigned long long best;
+  uint32_t bestp;
+  ChaseJob job[kChaseBatch];
+};
+// cand = c + (r & 0xFFFFFF) in one VALU.  (Inline asm: written in C++, as an and plus an add
+// or as a 24-bit multiply by 1 plus an add, the compiler emits the and and the add.)
+__device__ __forceinline__ uint32_t pack_candidate(uint32_t r, uint32_t c) {
+  uint32_t cand;
+  asm("v_mad_u32_u24 %0, %1, 1, %2" : "=v"(cand) : "v"(r), "v"(c));
+  return cand;
+}
+// a candidate that counts as a relaxation: its source holds a tuple and it is no padding copy
+__device__ __forceinline__ bool pack_counts(uint32_t cand) {
+  return (cand & 0xFFFFu) < kPackNoRank && (cand & 15u) != kPackPadM;
+}
+
 // The back key: the smallest key among the tight candidates (nd == b), as selects then a
 // tree of 3-input mins (v_min3_u32) -- the running min(c, tight ? key : ~0) compiles to a
 // compare, a min and a select per candidate (the lazy pull uses it)
@@ -241,7 +281,7 @@ __device__ __forceinline__ void pull_group(const RevView& rv, uint32_t lab, uint
 // every distance of the launch is an integer below 2^24 (pull_f32: integer arc weights,
 // max_len * max weight < 2^24), where every f32 sum, min and compare equals the f64 one.
 // Strings longer than in.max_len (a caller's wrong bound) are handed on, so the bound
-// always holds.
+// always holds.  RK 6: RK 3 with packed (distance, key) cells (PullLdsPacked above).
 template <int EW, int KP, bool DIRECT, int WAVES_PER_EU, int RK = 0>
 __global__ void __launch_bounds__(64, WAVES_PER_EU)
 eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
@@ -249,6 +289,8 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
   constexpr int W = 64 * EW;
   constexpr bool F32 = RK != 0 && RK != 4 && RK != 5;
   constexpr bool REC4 = RK >= 3;  // tier P's 4-B records (RK 4 / 5: f64 cells)
+  constexpr bool PACK = RK == 6;  // RK 3 with packed (distance, key) cells
+  static_assert(!PACK || (DIRECT && KP < (int)kPackPadM), "packed cells: direct layout, m = 15 is padding");
   constexpr int WT = RK == 5 ? (int)kPullWtMax : (int)kPullWt;  // weight-table entries
   using DT = typename std::conditional<F32, uint32_t, double>::type;  // (F32: integer cells)
   using RT = typename std::conditional<
@@ -257,18 +299,25 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
                                 typename std::conditional<F32, uint4, RevRec>::type>::type>::type;
   // key layout: rank word rank << 20 over y = j << 17 | m << 13 (RK 3: rank << 16 over
   // j << 13 | m << 9): the first key (rank << 3 | j) and m sit at these shifts
-  constexpr uint32_t kRankShift = REC4 ? 16 : 20;
+  // (packed cells: rank << 7 | j << 4 | m in the low half, the distance above)
+  constexpr uint32_t kRankShift = PACK ? 7 : REC4 ? 16 : 20;
   constexpr uint32_t kFirstShift = kRankShift - 3;
   constexpr uint32_t kMShift = kFirstShift - 4;
-  constexpr int kWords = PullLds<W, F32, WT>::kWords;
+  using LdsT = typename std::conditional<PACK, PullLdsPacked<W>, PullLds<W, F32, WT>>::type;
+  constexpr int kWords = LdsT::kWords;
+  // the rank word of a slot without a tuple, and the least first key that is none
+  constexpr uint32_t kAbsent = PACK ? kPackNoRank : kPullAbsent;
   static_assert(KP <= 16, "m is 4 bits of the key");
   static_assert(W < 512, "8 * slot is 12 bits of the key, ranks 9 bits");
-  __shared__ PullLds<W, F32, WT> S;
+  __shared__ LdsT S;
   const uint32_t lane = threadIdx.x;
-  const DT kInf = dist_inf<DT>();
+  const DT kInf = PACK ? (DT)(kPackAbsent >> 16) : dist_inf<DT>();
+  const uint32_t* const rpk = PACK ? rv_packed(rv) : nullptr;
   // a cell: {distance, rank word}
   auto set_cell = [&](uint32_t i, DT d, uint32_t rw) {
-    if constexpr (F32) {
+    if constexpr (PACK) {
+      S.cell[FB(i, W + 1, 153)] = ((uint32_t)d << 16) | rw;
+    } else if constexpr (F32) {
       S.cell[FB(i, W + 1, 153)] = make_uint2(d, rw);
     } else {
       S.d[FB(i, W + 1, 154)] = d;
@@ -276,7 +325,8 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
     }
   };
   auto rec = [&](uint32_t r) -> RT {
-    if constexpr (REC4) return rv.rrec4[r];
+    if constexpr (PACK) return rpk[r];
+    else if constexpr (REC4) return rv.rrec4[r];
     else if constexpr (RK == 2) return rv.rrec8[r];
     else if constexpr (F32) return rv.rrec32[r];
     else return rv.rrec[r];
@@ -317,7 +367,13 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         const uint2 h = hdr[k];
         if (!out.host_ol) out.out_il[jb.o + k] = in.labels[jb.off + k];
         uint32_t src8;
-        if constexpr (REC4) {
+        if constexpr (PACK) {
+          const uint32_t r = rpk[b];
+          out.out_ol[jb.o + k] = rv.rolab[b];
+          out.out_w[jb.o + k] = (double)((r >> 16) & 0xFFu) * rv.winv;  // exact: the f64 weight
+          tcur = tcur - (r >> 26) + (rv.rbias8 >> 3);  // the source: delta4 / 4 states back
+          src8 = tcur << 3;
+        } else if constexpr (REC4) {
           const uint32_t r = rv.rrec4[b];
           out.out_ol[jb.o + k] = rv.rolab[b];
           if constexpr (RK >= 4)
@@ -372,9 +428,9 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
   };
 
 #pragma unroll 1
-  for (uint32_t i = lane; i < (uint32_t)W + 1; i += 64) set_cell(i, kInf, kPullAbsent);
+  for (uint32_t i = lane; i < (uint32_t)W + 1; i += 64) set_cell(i, kInf, kAbsent);
   if (lane < (uint32_t)kWords) S.bits[FB(lane, kWords, 157)] = 0;
-  if constexpr (RK >= 4)
+  if constexpr (RK == 4 || RK == 5)
     for (uint32_t i = lane; i < (uint32_t)WT; i += 64) S.wt[i] = rv_weight_table(rv)[i];
   wave_lds_sync();
   uint32_t wlast = 0;  // uniform: cells [wlast, W] hold no tuple
@@ -403,7 +459,7 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
 
     // layer 0: the start tuple alone, slot 0 of a window at the start state
 #pragma unroll 1
-    for (uint32_t i = lane; i < wlast; i += 64) set_cell(i, kInf, kPullAbsent);
+    for (uint32_t i = lane; i < wlast; i += 64) set_cell(i, kInf, kAbsent);
     wave_lds_sync();
     if (lane == 0) set_cell(0, (DT)w_one(), 0u);
     wave_lds_sync();
@@ -458,12 +514,25 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         const uint32_t t = tn + i;
         uint32_t rec0, nb, xrec = 0;
         uint32_t tmin8 = tmin << 3;
+        RT rr[KP];
         if constexpr (DIRECT) {
           const uint32_t rs = *at_byte(rv.rlab, t * 4u);  // ilabel | min(nblocks, 255) << 24
+          if constexpr (PACK) {
+            // block 0's records, issued with the row word and before its first use (left to
+            // itself the scheduler put the first row's record loads behind the wait for the
+            // row word: two round trips to L2 in a row, every layer)
+            const uint32_t* const R = at_byte(rpk, t * (4u * KP));
+#pragma unroll
+            for (int m = 0; m < KP; ++m) rr[m] = R[m];
+            __builtin_amdgcn_sched_barrier(0);
+          }
           // block 0 holds the arcs of another label: shifting the window origin by 2^31
           // sends every source of the row past slot W (8 * state < 2^30), so the row
           // merges to "no tuple" with no per-result selects
-          const bool hit = (rs & 0xFFFFFFu) == lab && lab < kSpanMixed;
+          // (packed cells: a block without records is no padding past every window, so the
+          // row word of a state without in-arcs, 0xFFFFFF, must never hit; no rhs that has
+          // packed records carries that in-label, eager_pull.hip)
+          const bool hit = (rs & 0xFFFFFFu) == lab && lab < (PACK ? 0xFFFFFFu : kSpanMixed);
           tmin8 = hit ? tmin8 : tmin8 + 0x80000000u;
           rec0 = t * KP;
           nb = hit ? rs >> 24 : 0u;
@@ -472,47 +541,75 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         }
         // RK 3: the records hold the source relative to the target, so the lane's base is
         // 8 * (t - window origin) + rbias8 (the 2^31 shift of a miss applies the same)
-        if constexpr (REC4) tmin8 = (t << 3) - (tmin << 3) + rv.rbias8 + (tmin8 - (tmin << 3));
-        RT rr[KP];
-        // one base address, the records at immediate offsets
-        const RT* R;
-        // (RK 2, 3: the byte offset in 32 bits -- fewer than 2^28 records, eager_pull.hip)
-        if constexpr (REC4) R = at_byte(rv.rrec4, rec0 * 4u);
-        else if constexpr (RK == 2) R = at_byte(rv.rrec8, rec0 * 8u);
-        else if constexpr (F32) R = rv.rrec32 + rec0;
-        else R = rv.rrec + rec0;
+        // packed cells: 4-B cells, base4 = 4 * (t - window origin) + rbias8 / 2
+        if constexpr (PACK) tmin8 = (t << 2) - (tmin << 2) + (rv.rbias8 >> 1) + (tmin8 - (tmin << 3));
+        else if constexpr (REC4) tmin8 = (t << 3) - (tmin << 3) + rv.rbias8 + (tmin8 - (tmin << 3));
+        if constexpr (!PACK) {
+          // one base address, the records at immediate offsets
+          const RT* R;
+          // (RK 2, 3: the byte offset in 32 bits -- fewer than 2^28 records, eager_pull.hip)
+          if constexpr (REC4) R = at_byte(rv.rrec4, rec0 * 4u);
+          else if constexpr (RK == 2) R = at_byte(rv.rrec8, rec0 * 8u);
+          else if constexpr (F32) R = rv.rrec32 + rec0;
+          else R = rv.rrec + rec0;
 #pragma unroll
-        for (int m = 0; m < KP; ++m) rr[m] = R[m];
+          for (int m = 0; m < KP; ++m) rr[m] = R[m];
+        }
         uint32_t pk[KP], rw[KP];
         DT nd[KP];
         uint32_t f = kEmptyKey;
         DT b = kInf;
         uint32_t c = kEmptyKey;
-        // (one 64-bit min of (distance bits, key) per in-arc instead of fmin + the tight
-        // pass: 25 fewer VALU per unrolled row, same 41.4 ms per 1M metric strings, round 4)
+        if constexpr (PACK) {
+          // per in-arc: the source's cell (one SDWA subtract, one min), the candidate (one
+          // mad), and its share of the two min trees (v_min3_u32 / v_min3_u16)
+          // (the cells read in a loop of their own: the mads then wait for them once)
 #pragma unroll
-        for (int m = 0; m < KP; ++m) {
-          pull_candidate<W>(S, rr[m], tmin8, pk[m], nd[m], rw[m]);
-          f = min(f, pk[m]);
-          b = dist_min(b, nd[m]);
-        }
-        // the back key: the smallest key among the tight in-arcs (nd == b).  Integer cells:
-        // b - nd has its sign bit set exactly for the in-arcs above b (every nd >= b, and
-        // nd - b < 2^31), and a real key's bit 31 is clear (rank << 16, rank < 512), so
-        // OR-ing that bit into the key leaves only the tight ones in the running min -- one
-        // subtract and one v_and_or per in-arc instead of a compare (+ its SGPR-mask wait
-        // states) and a select: 26.70 -> 26.56 ms per 1M metric strings (A/B, one box).
-        // (tight_min's select-then-min3 tree measured 0.5 % slower here.)
-        if constexpr (F32 && !kTightSelect) {
+          for (int m = 0; m < KP; ++m) {
+            const uint32_t off = min(tmin8 - (rr[m] >> 24), 4u * W);
+            rw[m] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(S.cell) + FB(off, 4 * (W + 1), 152));
+          }
 #pragma unroll
-          for (int m = 0; m < KP; ++m) c = min(c, pk[m] | ((b - nd[m]) & 0x80000000u));
+          for (int m = 0; m < KP; ++m) pk[m] = pack_candidate(rr[m], rw[m]);
+          uint16_t f16 = (uint16_t)pk[0];
+          c = pk[0];
+#pragma unroll
+          for (int m = 1; m < KP; ++m) {
+            c = min(c, pk[m]);
+            f16 = __builtin_elementwise_min(f16, (uint16_t)pk[m]);
+          }
+          f = f16;
+          if (want_work()) {
+#pragma unroll
+            for (int m = 0; m < KP; ++m) relax += (uint32_t)__popcll(__ballot(pack_counts(pk[m])));
+          }
         } else {
+          // (one 64-bit min of (distance bits, key) per in-arc instead of fmin + the tight
+          // pass: 25 fewer VALU per unrolled row, same 41.4 ms per 1M metric strings, round 4)
 #pragma unroll
-          for (int m = 0; m < KP; ++m) c = min(c, nd[m] == b ? pk[m] : kEmptyKey);
-        }
-        if (want_work()) {
+          for (int m = 0; m < KP; ++m) {
+            pull_candidate<W>(S, rr[m], tmin8, pk[m], nd[m], rw[m]);
+            f = min(f, pk[m]);
+            b = dist_min(b, nd[m]);
+          }
+          // the back key: the smallest key among the tight in-arcs (nd == b).  Integer cells:
+          // b - nd has its sign bit set exactly for the in-arcs above b (every nd >= b, and
+          // nd - b < 2^31), and a real key's bit 31 is clear (rank << 16, rank < 512), so
+          // OR-ing that bit into the key leaves only the tight ones in the running min -- one
+          // subtract and one v_and_or per in-arc instead of a compare (+ its SGPR-mask wait
+          // states) and a select: 26.70 -> 26.56 ms per 1M metric strings (A/B, one box).
+          // (tight_min's select-then-min3 tree measured 0.5 % slower here.)
+          if constexpr (F32 && !kTightSelect) {
 #pragma unroll
-          for (int m = 0; m < KP; ++m) relax += (uint32_t)__popcll(__ballot(rw[m] < kPullAbsent));
+            for (int m = 0; m < KP; ++m) c = min(c, pk[m] | ((b - nd[m]) & 0x80000000u));
+          } else {
+#pragma unroll
+            for (int m = 0; m < KP; ++m) c = min(c, nd[m] == b ? pk[m] : kEmptyKey);
+          }
+          if (want_work()) {
+#pragma unroll
+            for (int m = 0; m < KP; ++m) relax += (uint32_t)__popcll(__ballot(rw[m] < kPullAbsent));
+          }
         }
         // the back record: RK 3 (direct layout) keeps one byte, the in-arc's position
         // x * KP + m in its target's group (block x, slot m; the chase re-derives the record
@@ -534,16 +631,32 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
                                     : (DIRECT ? rhs.num_states * KP : 0u);
 #pragma unroll
             for (int m = 0; m < KP; ++m) {
-              uint32_t p2, w2;
-              DT n2;
-              pull_candidate<W>(S, rec(rx + m), tmin8, p2, n2, w2);
-              f = min(f, p2);
-              if (n2 < b || (n2 == b && p2 < c)) {
-                b = n2;
-                c = p2;
-                ra = REC4 ? x * KP + m : rx + m;
+              if constexpr (PACK) {
+                // (an inactive lane's block holds no record: its candidate is dropped here)
+                const uint32_t r2 = rec(rx + m);
+                const uint32_t off = min(tmin8 - (r2 >> 24), 4u * W);
+                const uint32_t cl = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(S.cell) + FB(off, 4 * (W + 1), 152));
+                const uint32_t p2 = pack_candidate(r2, cl);
+                if (act) {
+                  f = min(f, p2 & 0xFFFFu);
+                  if (p2 < c) {
+                    c = p2;
+                    ra = x * KP + m;
+                  }
+                }
+                if (want_work()) relax += (uint32_t)__popcll(__ballot(act && pack_counts(p2)));
+              } else {
+                uint32_t p2, w2;
+                DT n2;
+                pull_candidate<W>(S, rec(rx + m), tmin8, p2, n2, w2);
+                f = min(f, p2);
+                if (n2 < b || (n2 == b && p2 < c)) {
+                  b = n2;
+                  c = p2;
+                  ra = REC4 ? x * KP + m : rx + m;
+                }
+                if (want_work()) relax += (uint32_t)__popcll(__ballot(w2 < kPullAbsent));
               }
-              if (want_work()) relax += (uint32_t)__popcll(__ballot(w2 < kPullAbsent));
             }
           }
         }
@@ -551,7 +664,7 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         bd[e] = b;
         bk[e] = c;
         bra[e] = ra;
-        if (f < kPullAbsent) {  // a tuple: mark its first key (rank << 3 | j)
+        if (f < kAbsent) {  // a tuple: mark its first key (rank << 3 | j)
           const uint32_t key = f >> kFirstShift;
           // (a 32-bit OR into the word's half: ~4 lanes of a row share an address instead
           // of ~8, and same-address LDS atomics serialise -- they were all of the kernel's
@@ -592,7 +705,7 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         if ((uint32_t)e >= rows_w) continue;  // uniform
         const uint32_t i = (uint32_t)e * 64 + lane;
         if ((uint32_t)e >= rows_n) {  // uniform: a row past the next layer's window, emptied
-          set_cell(i, bd[e], kPullAbsent);
+          set_cell(i, bd[e], kAbsent);
           continue;
         }
         // (the row test as its own uniform branch: folded into pres, the compiler kept it
@@ -600,13 +713,17 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         uint32_t fe = fst[e];
         asm volatile("" : "+v"(fe));  // (a fresh compare here: P1's, kept across P2 under
                                       // another exec mask, was rebuilt with 2 VALU)
-        const bool pres = fe < kPullAbsent;
+        const bool pres = fe < kAbsent;
         const uint32_t key = pres ? fe >> kFirstShift : 0u;
         const uint2 p = reinterpret_cast<const uint2*>(S.pre)[FB(key >> 5, 2 * kWords, 162)];
         const uint32_t rank = p.x + (uint32_t)__popc(p.y & ((1u << (key & 31u)) - 1u));
         // (an absent slot keeps its merged distance, +inf or >= kDistAbsent: no select; the
         // rank word alone marks it absent)
-        set_cell(i, bd[e], pres ? rank << kRankShift : kPullAbsent);
+        // (packed cells: the merged word's distance half under the new rank)
+        if constexpr (PACK)
+          S.cell[FB(i, W + 1, 153)] = (bk[e] & 0xFFFF0000u) | (pres ? rank << kRankShift : kAbsent);
+        else
+          set_cell(i, bd[e], pres ? rank << kRankShift : kPullAbsent);
         const unsigned long long pm = __ballot(pres);
         if (pm) {
           lo_slot = min(lo_slot, (uint32_t)e * 64 + (uint32_t)__builtin_ctzll(pm));
@@ -620,9 +737,10 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
           if (last) {  // final candidates, lexmin (total, rank) within the lane
             const uint32_t t = tn + i;
             const double fw2 = rhs.final_w[FB(t, rhs.num_states, 62)];
-            if (!w_is_zero((double)bd[e]) && !w_is_zero(fw2)) {
+            const DT de = PACK ? (DT)(bk[e] >> 16) : bd[e];
+            if (!w_is_zero((double)de) && !w_is_zero(fw2)) {
               // times(d, times(One, fw2)), in f64 (f32 cells hold d exactly, scaled by 2^k)
-              const unsigned long long kk = okey((double)bd[e] * (F32 ? rv.winv : 1.0) + fw2);
+              const unsigned long long kk = okey((double)de * (F32 ? rv.winv : 1.0) + fw2);
               const uint32_t pp = (rank << 9) | i;
               if (kk < mykey || (kk == mykey && pp < myp)) {
                 mykey = kk;
