@@ -144,6 +144,69 @@ FstError fst_pipeline_batch(const FstHandle* stages, uint32_t num_stages, const 
                             const uint64_t* offsets, uint32_t num_strings, uint32_t n,
                             const FstBatchOptions* opts, FstBatchResult* out);
 
+/* Text in, text out: the loop the reference application runs per utterance and stage,
+ *   fst_compile_string(bytes) -> fst_compose_frozen_shortest_path -> fst_print_output_string
+ * (README.md:177-214, src/string.zig:17-97), for a whole batch with bytes on both sides of
+ * the bus: 1 B per input byte up instead of a 4-B label, and per string its status, offset,
+ * total weight and output bytes down instead of 16 B per path arc.
+ *
+ * Input: string i is text[offsets[i] .. offsets[i+1]); its stage-1 labels are byte + 1
+ * (compileString), every byte value is legal, an empty string is the one-state final
+ * acceptor.  n is 1; one stage runs as fst_compose_frozen_shortest_path_batch does, several
+ * as fst_pipeline_batch does.
+ * Output, for every producer below (device emission, host conversion):
+ *   - an OK string's bytes are the last stage's path olabels in path order, epsilons
+ *     dropped, each minus 1 (printStringFromTape(.output));
+ *   - an olabel above 256 is no byte: the string is FST_PATH_UNSUPPORTED;
+ *   - every non-OK string has zero bytes and total_weight = +inf; a string that failed at
+ *     an earlier stage reports that stage's status;
+ *   - total_weight is the reference search's own best total, the f64 left fold
+ *     ((0.0 + w_1) + w_2 ... + w_L) + final_weight over the path's arcs (dist of
+ *     shortest-path.zig:72, then times(dist, final)), bit for bit. */
+typedef struct {
+    uint32_t num_strings;
+    int32_t* status;          /* [num_strings] FstPathStatus */
+    uint64_t* text_offsets;   /* [num_strings + 1] CSR offsets into text */
+    uint8_t* text;            /* [total_bytes] */
+    double* total_weight;     /* [num_strings] */
+    uint64_t total_bytes;
+} FstTextResult;
+
+/* Host bytes in, host bytes out.  Arguments are checked as by fst_pipeline_batch
+ * (FST_INVALID_ARG for a bad handle, decreasing offsets, num_stages == 0 or unknown flags;
+ * *out is zeroed once they are checked); num_strings == 0 gives an empty OK result.
+ * Semantics, device and FST_BATCH_DEVICES sharding from opts, as for the label entries
+ * (shards balanced by fst_chain_cost of stage 1; the result is in input order and
+ * byte-identical to a one-shard run).  Each shard uploads bytes and offsets, widens them to
+ * labels on the device, runs the stages, emits the text on the device and downloads only the
+ * four result arrays.  The result lives in pooled pinned blocks until fst_text_result_free. */
+FstError fst_normalize_text_batch(const FstHandle* stages, uint32_t num_stages,
+                                  const uint8_t* text, const uint64_t* offsets,
+                                  uint32_t num_strings, const FstBatchOptions* opts,
+                                  FstTextResult* out);
+void fst_text_result_free(FstTextResult* r);
+
+/* The device-resident pieces (every d_ pointer is device memory on the current device).
+ * fst_device_compile_text: d_labels[k] = d_text[k] + 1 for k in [d_offsets[0],
+ * d_offsets[num_strings]), so d_offsets serves the labels too; asynchronous on `stream`.
+ * Nothing outside that range is read or written. */
+FstError fst_device_compile_text(const uint8_t* d_text, const uint64_t* d_offsets,
+                                 uint32_t num_strings, uint32_t* d_labels, void* stream);
+/* fst_device_emit_text: a finished stage as text (d_text_offsets [num_strings + 1], d_status
+ * and d_total_weight [num_strings]).  Synchronises `stream`.  *total_bytes (host) receives
+ * the bytes the batch needs; no byte at or past text_capacity is written, so when
+ * *total_bytes > text_capacity the text is incomplete (offsets, statuses and weights are
+ * not): call again with a buffer of *total_bytes. */
+FstError fst_device_emit_text(const FstDeviceBatch* stage, uint32_t num_strings,
+                              uint8_t* d_text, uint64_t text_capacity,
+                              uint64_t* d_text_offsets, int32_t* d_status,
+                              double* d_total_weight, uint64_t* total_bytes, void* stream);
+
+/* Host conversion of a label result to text, same semantics, no GPU needed (the result is
+ * freed with fst_text_result_free all the same).  FST_INVALID_ARG for a null argument or
+ * decreasing path offsets. */
+FstError fst_batch_result_to_text(const FstBatchResult* in, FstTextResult* out);
+
 /* Bring a frozen FST's device copy up on `device` (blob H2D + on-device SoA mirror). */
 FstError fst_device_prepare(FstHandle b, int32_t device);
 /* Adopt a blob that already sits in device memory on `device` (e.g. received by an

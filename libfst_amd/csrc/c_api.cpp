@@ -771,7 +771,8 @@ struct Shard {
   std::unique_ptr<DevOut> keep;
   std::unique_ptr<DevBuf> fail;  // pipelines: the first failing stage per string
   std::unique_ptr<DevBuf> st, off, fin, il, ol, w;
-  uint64_t tot = 0;
+  std::unique_ptr<DevBuf> text;  // text entries: the emitted bytes (fin: the total weights)
+  uint64_t tot = 0;              // arcs of the compacted shard (text entries: bytes)
   FstError err = FST_OK;
   LaunchStats stats;
 };
@@ -1520,13 +1521,24 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b,
   return FST_OK;
 }
 
+// What becomes of a computed shard: `compact` (on the shard's lease, after the engines) brings
+// its result into CSR order on the device and sets S.tot; `alloc` makes the host result once
+// every shard's total is known; `download` copies a shard in at its string range and at the
+// sum of the earlier shards' totals; `finish` closes the offsets.
+struct ShardSink {
+  std::function<FstError(Shard&)> compact;
+  std::function<bool(uint64_t)> alloc;
+  std::function<FstError(Shard&, uint64_t)> download;
+  std::function<void(uint64_t)> finish;
+};
+
 // Runs `compute` (the engines: it fills S.keep and, for pipelines, S.fail) over the shards
-// of a batch and gathers their results into *out.  Shards are contiguous string ranges of
+// of a batch and gathers their results through `sink`.  Shards are contiguous string ranges of
 // equal estimated cost (cost[i]: the work estimate of string i); shard j runs on
 // devices[j % devices.size()] on a host thread of its own (inline for one shard).
 FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
                      const std::vector<double>& cost,
-                     const std::function<FstError(Shard&)>& compute, FstBatchResult* out) {
+                     const std::function<FstError(Shard&)>& compute, const ShardSink& sink) {
   // shard 0 runs on the calling thread and switches its current device: give the caller
   // its device back on every return (later calls that use current_device() rely on it)
   DeviceRestore_ restore;
@@ -1574,7 +1586,7 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
     S.err = compute(S);
     S.stats = t_last_stats;
     if (S.err == FST_OK && !S.keep) S.err = FST_OOM;
-    if (S.err == FST_OK) S.err = shard_compact(S);
+    if (S.err == FST_OK) S.err = sink.compact(S);
     // no lease is held between the phases: a shard waiting for an engine never holds one
     // (two sharded calls on one device cannot deadlock)
     S.E = DeviceEngine::Lease();
@@ -1585,7 +1597,7 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
       return;
     }
     S.E = DeviceEngine::acquire(S.dev);
-    S.err = S.E ? shard_download(S, out, base) : FST_OOM;
+    S.err = S.E ? sink.download(S, base) : FST_OOM;
     S.E = DeviceEngine::Lease();
   };
   auto each = [&](const std::function<void(uint32_t)>& f) {
@@ -1602,11 +1614,11 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
     tot += S.tot;
   }
   if (t_prof) t_prof->lap(4);
-  if (!alloc_result(out, num, tot)) return FST_OOM;
+  if (!sink.alloc(tot)) return FST_OOM;
   std::vector<uint64_t> base(nsh, 0);
   for (uint32_t j = 1; j < nsh; ++j) base[j] = base[j - 1] + sh[j - 1].tot;
   each([&](uint32_t j) { phase2(sh[j], base[j]); });
-  out->path_offsets[num] = tot;
+  sink.finish(tot);
   LaunchStats agg = sh[0].stats;  // the slowest shard's kernel time, launches summed
   for (uint32_t j = 1; j < nsh; ++j) {
     agg.kernel_ms = std::max(agg.kernel_ms, sh[j].stats.kernel_ms);
@@ -1616,6 +1628,69 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
   for (Shard& S : sh)
     if (S.err != FST_OK) return S.err;
   if (t_prof) t_prof->lap(3);
+  return FST_OK;
+}
+
+// ... into a label result: compact_paths on the device, then the arc arrays by DMA.
+FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
+                     const std::vector<double>& cost,
+                     const std::function<FstError(Shard&)>& compute, FstBatchResult* out) {
+  const ShardSink sink{shard_compact,
+                       [=](uint64_t tot) { return alloc_result(out, num, tot); },
+                       [=](Shard& S, uint64_t base) { return shard_download(S, out, base); },
+                       [=](uint64_t tot) { out->path_offsets[num] = tot; }};
+  return run_sharded(devices, nsh, num, cost, compute, sink);
+}
+
+// ---- Text results (fst_normalize_text_batch) -------------------------------------------
+// The text phase of a shard, in compact_paths' place: count and scan the output bytes of the
+// last stage's paths, then write them (DeviceEngine::text_count / text_write).
+FstError shard_text(Shard& S) {
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  const DevOut& o = *S.keep;
+  S.st = std::make_unique<DevBuf>(num * 4ull);
+  S.off = std::make_unique<DevBuf>((num + 1ull) * 8);
+  S.fin = std::make_unique<DevBuf>(num * 8ull);
+  if (!S.st->p || !S.off->p || !S.fin->p) return FST_OOM;
+  if (S.E->text_count(o.v, num, S.fail ? (const int32_t*)S.fail->p : nullptr, (int32_t*)S.st->p,
+                      (uint64_t*)S.off->p, (double*)S.fin->p, &S.tot, stream) != hipSuccess)
+    return FST_OOM;
+  S.text = std::make_unique<DevBuf>(S.tot);
+  if (!S.text->p) return FST_OOM;
+  // (synchronised: the download may run on another engine's stream)
+  if (S.E->text_write(o.v, num, (const int32_t*)S.st->p, (const uint64_t*)S.off->p,
+                      (uint8_t*)S.text->p, S.tot, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return FST_OOM;
+  S.keep.reset();  // the path arena is not downloaded
+  return FST_OK;
+}
+
+bool alloc_text_result(FstTextResult* out, uint32_t num, uint64_t tot) {
+  out->num_strings = num;
+  out->total_bytes = tot;
+  out->status = (int32_t*)pin_alloc(std::max<size_t>(num, 1) * 4);
+  out->text_offsets = (uint64_t*)pin_alloc((num + 1ull) * 8);
+  out->total_weight = (double*)pin_alloc(std::max<size_t>(num, 1) * 8);
+  out->text = (uint8_t*)pin_alloc(std::max<uint64_t>(tot, 1));
+  return out->status && out->text_offsets && out->total_weight && out->text;
+}
+
+FstError shard_text_download(Shard& S, FstTextResult* out, uint64_t byte_base) {
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  const auto d2h = [stream](void* dst, const void* src, size_t b) {
+    return b == 0 || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, stream) == hipSuccess;
+  };
+  if (!(d2h(out->status + S.s0, S.st->p, num * 4ull) &&
+        d2h(out->total_weight + S.s0, S.fin->p, num * 8ull) &&
+        d2h(out->text_offsets + S.s0, S.off->p, num * 8ull) &&
+        d2h(out->text + byte_base, S.text->p, S.tot)) ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return FST_OOM;
+  if (byte_base)
+    for (uint32_t i = S.s0; i < S.s1; ++i) out->text_offsets[i] += byte_base;
   return FST_OK;
 }
 
@@ -2461,6 +2536,9 @@ FstError fst_device_project_output(const FstDeviceBatch* o, uint32_t num_strings
 }
 
 namespace {
+FstError run_pipeline_stages(Shard& S, const std::vector<std::shared_ptr<FrozenFst>>& fs,
+                             std::unique_ptr<DevBuf> lab, std::unique_ptr<DevBuf> off,
+                             uint64_t in_total, uint32_t max_len, uint32_t n, int semantics);
 // One shard of a pipeline: every stage on the shard's device, each stage's 1-best output tape
 // projected into the next stage's inputs on the device; S.keep = the last stage's outputs,
 // S.fail = the first failing stage per string.
@@ -2468,7 +2546,6 @@ FstError run_pipeline_shard(Shard& S, const std::vector<std::shared_ptr<FrozenFs
                             const uint32_t* labels, const uint64_t* offsets, uint32_t n,
                             int semantics) {
   DeviceEngine::Lease& E = S.E;
-  const int dev = S.dev;
   const uint32_t num_strings = S.s1 - S.s0;
   const hipStream_t stream = E.stream();
   // stage-1 inputs
@@ -2486,12 +2563,63 @@ FstError run_pipeline_shard(Shard& S, const std::vector<std::shared_ptr<FrozenFs
   if (hipMemcpyAsync(off->p, rebased.data(), (num_strings + 1ull) * 8, hipMemcpyHostToDevice,
                      stream) != hipSuccess)
     return FST_OOM;
+  if (t_prof) t_prof->lap(0);
+  return run_pipeline_stages(S, fs, std::move(lab), std::move(off), total, max_len, n, semantics);
+}
+
+// The text entry's shard: the bytes and their offsets go up as they are, the device widens
+// them to stage-1 labels (DeviceEngine::widen_text), then the same stages.
+FstError run_text_shard(Shard& S, const std::vector<std::shared_ptr<FrozenFst>>& fs,
+                        const uint8_t* text, const uint64_t* offsets, int semantics) {
+  DeviceEngine::Lease& E = S.E;
+  const uint32_t num_strings = S.s1 - S.s0;
+  const hipStream_t stream = E.stream();
+  const uint64_t total = num_strings ? offsets[num_strings] - offsets[0] : 0;
+  uint32_t max_len = 0;
+  std::vector<uint64_t> rebased(num_strings + 1);
+  for (uint32_t i = 0; i <= num_strings; ++i) rebased[i] = offsets[i] - offsets[0];
+  for (uint32_t i = 0; i < num_strings; ++i)
+    max_len = std::max<uint32_t>(max_len, (uint32_t)(rebased[i + 1] - rebased[i]));
+  // `bytes` is read by the widen kernel only; it and `rebased` live until the first stage
+  // has synchronised the stream, and every failure drains the stream before they go
+  struct Drain {
+    hipStream_t s;
+    bool done = false;
+    ~Drain() {
+      if (!done) (void)hipStreamSynchronize(s);
+    }
+  } drain{stream};
+  DevBuf bytes(total);
+  auto lab = std::make_unique<DevBuf>(total * 4), off = std::make_unique<DevBuf>((num_strings + 1ull) * 8);
+  if (!bytes.p || !lab->p || !off->p) return FST_OOM;
+  if (total && hipMemcpyAsync(bytes.p, text + offsets[0], total, hipMemcpyHostToDevice, stream) !=
+                   hipSuccess)
+    return FST_OOM;
+  if (hipMemcpyAsync(off->p, rebased.data(), (num_strings + 1ull) * 8, hipMemcpyHostToDevice,
+                     stream) != hipSuccess)
+    return FST_OOM;
+  if (E->widen_text((const uint8_t*)bytes.p, (const uint64_t*)off->p, num_strings,
+                    (uint32_t*)lab->p, stream) != hipSuccess)
+    return FST_OOM;
+  if (t_prof) t_prof->lap(0);
+  const FstError e =
+      run_pipeline_stages(S, fs, std::move(lab), std::move(off), total, max_len, 1, semantics);
+  drain.done = e == FST_OK;  // (run_chain_batch_dev synchronised it)
+  return e;
+}
+
+// The stages of one shard on device inputs (labels `lab`, offsets `off`, in_total labels).
+FstError run_pipeline_stages(Shard& S, const std::vector<std::shared_ptr<FrozenFst>>& fs,
+                             std::unique_ptr<DevBuf> lab, std::unique_ptr<DevBuf> off,
+                             uint64_t in_total, uint32_t max_len, uint32_t n, int semantics) {
+  DeviceEngine::Lease& E = S.E;
+  const int dev = S.dev;
+  const uint32_t num_strings = S.s1 - S.s0;
+  const hipStream_t stream = E.stream();
   S.fail = std::make_unique<DevBuf>(num_strings * 4ull);  // first failing stage per string
   if (!S.fail->p || hipMemsetAsync(S.fail->p, 0, num_strings * 4ull, stream) != hipSuccess)
     return FST_OOM;
-  uint64_t in_total = total;
   HostPaths h;
-  if (t_prof) t_prof->lap(0);
   for (size_t k = 0; k < fs.size(); ++k) {
     DeviceFst* D = fs[k]->device(dev);
     if (!D) return FST_OOM;
@@ -2569,6 +2697,154 @@ FstError fst_pipeline_batch(const FstHandle* stages, uint32_t num_stages, const 
   }
   prof.lap(5);
   prof.print("fst_pipeline_batch");
+  return FST_OK;
+}
+
+// ---- Text entries (fst_batch.h) ---------------------------------------------------------
+
+FstError fst_normalize_text_batch(const FstHandle* stages, uint32_t num_stages,
+                                  const uint8_t* text, const uint64_t* offsets,
+                                  uint32_t num_strings, const FstBatchOptions* opts,
+                                  FstTextResult* out) {
+  if (!out || !stages || num_stages == 0 || !offsets ||
+      (!text && num_strings && offsets[num_strings] != offsets[0]))
+    return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  for (uint32_t i = 0; i < num_strings; ++i)
+    if (offsets[i + 1] < offsets[i]) return FST_INVALID_ARG;
+  if (opts && (opts->flags & ~FST_BATCH_DEVICES)) return FST_INVALID_ARG;
+  std::vector<std::shared_ptr<FrozenFst>> fs(num_stages);
+  for (uint32_t k = 0; k < num_stages; ++k)
+    if (!(fs[k] = g_fst.get(stages[k]))) return FST_INVALID_ARG;
+  if (num_strings == 0) {  // nothing to run: the empty result
+    if (!alloc_text_result(out, 0, 0)) {
+      fst_text_result_free(out);
+      return FST_OOM;
+    }
+    out->text_offsets[0] = 0;
+    return FST_OK;
+  }
+  if (!gpu_available()) return FST_INVALID_ARG;
+  const int semantics = opts ? (int)opts->semantics : FST_SEM_LAZY;
+  std::vector<int> devices;
+  uint32_t nsh = 1;
+  if (FstError e = batch_devices(opts, &devices, &nsh); e != FST_OK) return e;
+  HostProf prof;
+  t_prof = &prof;
+  struct ProfScope {
+    ~ProfScope() { t_prof = nullptr; }
+  } prof_scope;
+  std::vector<double> cost(nsh > 1 ? num_strings : 0);
+  for (size_t i = 0; i < cost.size(); ++i) cost[i] = fs[0]->chain_cost(offsets[i + 1] - offsets[i]);
+  const ShardSink sink{
+      shard_text, [=](uint64_t tot) { return alloc_text_result(out, num_strings, tot); },
+      [=](Shard& S, uint64_t base) { return shard_text_download(S, out, base); },
+      [=](uint64_t tot) { out->text_offsets[num_strings] = tot; }};
+  const FstError e = run_sharded(
+      devices, nsh, num_strings, cost,
+      [&](Shard& S) { return run_text_shard(S, fs, text, offsets + S.s0, semantics); }, sink);
+  if (e != FST_OK) {
+    fst_text_result_free(out);
+    return e;
+  }
+  prof.lap(5);
+  prof.print("fst_normalize_text_batch");
+  return FST_OK;
+}
+
+void fst_text_result_free(FstTextResult* r) {
+  if (!r) return;
+  pin_release(r->status);
+  pin_release(r->text_offsets);
+  pin_release(r->text);
+  pin_release(r->total_weight);
+  std::memset(r, 0, sizeof(*r));
+}
+
+FstError fst_device_compile_text(const uint8_t* d_text, const uint64_t* d_offsets,
+                                 uint32_t num_strings, uint32_t* d_labels, void* stream) {
+  if (!d_offsets) return FST_INVALID_ARG;
+  if (!gpu_available()) return FST_INVALID_ARG;
+  const int dev = current_device();
+  if (dev < 0) return FST_INVALID_ARG;
+  DeviceEngine::Lease E = DeviceEngine::acquire(dev);
+  if (!E) return FST_INVALID_ARG;
+  const hipStream_t s = E.use((hipStream_t)stream);
+  return E->widen_text(d_text, d_offsets, num_strings, d_labels, s) == hipSuccess ? FST_OK
+                                                                                 : FST_OOM;
+}
+
+FstError fst_device_emit_text(const FstDeviceBatch* o, uint32_t num_strings, uint8_t* d_text,
+                              uint64_t text_capacity, uint64_t* d_text_offsets,
+                              int32_t* d_status, double* d_total_weight, uint64_t* total_bytes,
+                              void* stream) {
+  if (!o || !d_text_offsets || !d_status || !d_total_weight || (text_capacity && !d_text))
+    return FST_INVALID_ARG;
+  if (!gpu_available()) return FST_INVALID_ARG;
+  const int dev = current_device();
+  if (dev < 0) return FST_INVALID_ARG;
+  BatchOutDev v{o->status, o->path_len, o->path_offset, o->final_weight, o->ilabels,
+                o->olabels, o->weights, o->arc_capacity,
+                (unsigned long long*)o->arc_cursor, o->work};
+  DeviceEngine::Lease E = DeviceEngine::acquire(dev);
+  if (!E) return FST_INVALID_ARG;
+  const hipStream_t s = E.use((hipStream_t)stream);
+  uint64_t tot = 0;
+  if (E->text_count(v, num_strings, nullptr, d_status, d_text_offsets, d_total_weight, &tot, s) !=
+          hipSuccess ||
+      E->text_write(v, num_strings, d_status, d_text_offsets, d_text, text_capacity, s) !=
+          hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return FST_OOM;
+  if (total_bytes) *total_bytes = tot;
+  return FST_OK;
+}
+
+FstError fst_batch_result_to_text(const FstBatchResult* in, FstTextResult* out) {
+  if (!in || !out) return FST_INVALID_ARG;
+  const uint32_t num = in->num_strings;
+  if (num && (!in->status || !in->path_offsets || !in->final_weights)) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  for (uint32_t i = 0; i < num; ++i)
+    if (in->path_offsets[i + 1] < in->path_offsets[i]) return FST_INVALID_ARG;
+  if (num && in->path_offsets[num] != in->path_offsets[0] && (!in->olabels || !in->weights))
+    return FST_INVALID_ARG;
+  // pass 1: statuses and byte counts; pass 2: the bytes and the fold
+  std::vector<int32_t> st(num);
+  std::vector<uint64_t> cnt(num, 0);
+  uint64_t tot = 0;
+  for (uint32_t i = 0; i < num; ++i) {
+    st[i] = in->status[i];
+    if (st[i] != kPathOk) continue;
+    uint64_t c = 0;
+    for (uint64_t k = in->path_offsets[i]; k < in->path_offsets[i + 1]; ++k) {
+      if (in->olabels[k] > 256u) {
+        st[i] = kPathUnsupported;
+        break;
+      }
+      c += in->olabels[k] != kEpsilon;
+    }
+    if (st[i] == kPathOk) cnt[i] = c;
+    tot += cnt[i];
+  }
+  if (!alloc_text_result(out, num, tot)) {
+    fst_text_result_free(out);
+    return FST_OOM;
+  }
+  uint64_t w = 0;
+  for (uint32_t i = 0; i < num; ++i) {
+    out->status[i] = st[i];
+    out->text_offsets[i] = w;
+    out->total_weight[i] = w_zero();
+    if (st[i] != kPathOk) continue;
+    double d = w_one();
+    for (uint64_t k = in->path_offsets[i]; k < in->path_offsets[i + 1]; ++k) {
+      if (in->olabels[k] != kEpsilon) out->text[w++] = (uint8_t)(in->olabels[k] - 1u);
+      d = w_times(d, in->weights[k]);
+    }
+    out->total_weight[i] = w_times(d, in->final_weights[i]);
+  }
+  out->text_offsets[num] = w;
   return FST_OK;
 }
 

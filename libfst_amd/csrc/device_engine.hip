@@ -24,6 +24,7 @@
 #include "kernels/eager_window.hpp"
 #include "kernels/lazy_wave.hpp"
 #include "kernels/lazy_tiny.hpp"
+#include "kernels/text_io.hpp"
 
 #define HIP_TRY(x)                              \
   do {                                          \
@@ -2554,6 +2555,42 @@ hipError_t DeviceEngine::compact_paths(const BatchOutDev& s, uint32_t num, const
   }
   HIP_TRY(hipMemcpyAsync(total, offsets + num, 8, hipMemcpyDeviceToHost, stream));
   return hipStreamSynchronize(stream);
+}
+
+hipError_t DeviceEngine::widen_text(const uint8_t* text, const uint64_t* offsets, uint32_t num,
+                                    uint32_t* labels, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(dev_));
+  // (the batch's length sits on the device: a fixed grid strides over it)
+  text_widen_kernel<<<(uint32_t)num_cus_ * 8, 256, 0, stream>>>(text, offsets, num, labels);
+  return hipGetLastError();
+}
+
+hipError_t DeviceEngine::text_count(const BatchOutDev& s, uint32_t num, const int32_t* fail,
+                                    int32_t* status, uint64_t* offsets, double* total_w,
+                                    uint64_t* total, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(dev_));
+  uint64_t* counts = (uint64_t*)scratch(kProjCount, ((size_t)num + 1) * 8 + 16);
+  if (!counts) return hipErrorOutOfMemory;
+  const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(num, (uint32_t)num_cus_ * 32));
+  text_count_kernel<<<grid, 64, 0, stream>>>(s, num, fail, status, counts, total_w);
+  HIP_TRY(hipGetLastError());
+  size_t tbytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tbytes, counts, offsets, num + 1, stream));
+  void* temp = scratch(kProjTemp, tbytes + 16);
+  if (!temp) return hipErrorOutOfMemory;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(temp, tbytes, counts, offsets, num + 1, stream));
+  HIP_TRY(hipMemcpyAsync(total, offsets + num, 8, hipMemcpyDeviceToHost, stream));
+  return hipStreamSynchronize(stream);
+}
+
+hipError_t DeviceEngine::text_write(const BatchOutDev& s, uint32_t num, const int32_t* status,
+                                    const uint64_t* offsets, uint8_t* text, uint64_t cap,
+                                    hipStream_t stream) {
+  HIP_TRY(hipSetDevice(dev_));
+  if (!num) return hipSuccess;
+  const uint32_t grid = std::min<uint32_t>(num, (uint32_t)num_cus_ * 32);
+  text_write_kernel<<<grid, 64, 0, stream>>>(s, num, status, offsets, text, cap);
+  return hipGetLastError();
 }
 
 hipError_t DeviceEngine::merge_status(int32_t* fail, const int32_t* st, uint32_t num,

@@ -404,6 +404,20 @@ class DeviceEngine {
                            int32_t* status, uint64_t* offsets, uint32_t* il, uint32_t* ol,
                            double* w, double* fin, uint64_t out_cap, uint64_t* total,
                            hipStream_t stream);
+  // Text entries (kernels/text_io.hpp).  widen_text: labels[k] = text[k] + 1 over
+  // [offsets[0], offsets[num]) (compileString for the batch), asynchronous on `stream`.
+  hipError_t widen_text(const uint8_t* text, const uint64_t* offsets, uint32_t num,
+                        uint32_t* labels, hipStream_t stream);
+  // A finished (last) stage as text, step 1: per string its status (`fail` as in
+  // compact_paths; UNSUPPORTED for an olabel > 256), its byte count scanned into
+  // offsets[num + 1], and total_w = the serial fold of the path's weights and the final
+  // weight (+inf unless OK).  Synchronises on `stream`; *total = the bytes of the batch.
+  hipError_t text_count(const BatchOutDev& s, uint32_t num, const int32_t* fail, int32_t* status,
+                        uint64_t* offsets, double* total_w, uint64_t* total, hipStream_t stream);
+  // Step 2: the OK strings' bytes (non-epsilon olabels - 1) at their offsets; no byte at or
+  // past `cap` is written.  Asynchronous on `stream`.
+  hipError_t text_write(const BatchOutDev& s, uint32_t num, const int32_t* status,
+                        const uint64_t* offsets, uint8_t* text, uint64_t cap, hipStream_t stream);
   // fail[i] = st[i] where fail[i] is still OK (the first failing stage wins).
   hipError_t merge_status(int32_t* fail, const int32_t* st, uint32_t num, hipStream_t stream);
   // fst_shortest_path on an explicit graph; `g` holds the FST itself (CSR, arcs in

@@ -43,6 +43,12 @@ class FstBatchResult(C.Structure):
                 ("final_weights", C.POINTER(C.c_double)), ("total_arcs", C.c_uint64)]
 
 
+class FstTextResult(C.Structure):
+    _fields_ = [("num_strings", C.c_uint32), ("status", C.POINTER(C.c_int32)),
+                ("text_offsets", C.POINTER(C.c_uint64)), ("text", C.POINTER(C.c_uint8)),
+                ("total_weight", C.POINTER(C.c_double)), ("total_bytes", C.c_uint64)]
+
+
 FST_BATCH_DEVICES = 1
 
 
@@ -128,6 +134,14 @@ SIGNATURES = {
                                             C.POINTER(_u32), C.c_void_p]),
     "fst_pipeline_batch": (C.c_int, [C.c_void_p, _u32, C.c_void_p, C.c_void_p, _u32, _u32,
                                      C.c_void_p, C.c_void_p]),
+    "fst_normalize_text_batch": (C.c_int, [C.c_void_p, _u32, C.c_void_p, C.c_void_p, _u32,
+                                           C.POINTER(FstBatchOptions), C.POINTER(FstTextResult)]),
+    "fst_text_result_free": (None, [C.POINTER(FstTextResult)]),
+    "fst_device_compile_text": (C.c_int, [C.c_void_p, C.c_void_p, _u32, C.c_void_p, C.c_void_p]),
+    "fst_device_emit_text": (C.c_int, [C.POINTER(FstDeviceBatch), _u32, C.c_void_p, _u64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_u64),
+                                       C.c_void_p]),
+    "fst_batch_result_to_text": (C.c_int, [C.POINTER(FstBatchResult), C.POINTER(FstTextResult)]),
 }
 
 _lib = None
@@ -411,6 +425,103 @@ def _take_result(res, num) -> BatchResult:
                        olabels=arr(res.olabels, tot, np.uint32, C.c_uint32),
                        weights=arr(res.weights, tot, np.float64, C.c_double),
                        finals=arr(res.final_weights, num, np.float64, C.c_double))
+
+
+@dataclass
+class TextResult:
+    status: np.ndarray
+    offsets: np.ndarray
+    text: np.ndarray
+    total_weight: np.ndarray
+
+    def texts(self):
+        """One `bytes` per string (empty for every string that is not FST_PATH_OK)."""
+        raw, off = self.text.tobytes(), self.offsets
+        return [raw[int(off[i]):int(off[i + 1])] for i in range(len(off) - 1)]
+
+
+class _TextOwner:
+    """Owns one FstTextResult; fst_text_result_free runs once no array views it."""
+
+    def __init__(self, res):
+        self.res = res
+
+    def __del__(self):
+        try:
+            lib().fst_text_result_free(C.byref(self.res))
+        except Exception:  # interpreter shutdown
+            pass
+
+
+def _take_text(res) -> TextResult:
+    num, tot = int(res.num_strings), int(res.total_bytes)
+    owner = _TextOwner(res)
+
+    def arr(p, cnt, dt, ct):
+        if cnt == 0:
+            return np.zeros(0, dt)
+        buf = (ct * cnt).from_address(C.cast(p, C.c_void_p).value)
+        buf._owner = owner  # the view keeps the result alive
+        return np.frombuffer(buf, dtype=dt)
+
+    return TextResult(status=arr(res.status, num, np.int32, C.c_int32),
+                      offsets=arr(res.text_offsets, num + 1, np.uint64, C.c_uint64),
+                      text=arr(res.text, tot, np.uint8, C.c_uint8),
+                      total_weight=arr(res.total_weight, num, np.float64, C.c_double))
+
+
+def text_csr(texts):
+    """(uint8 array, uint64 offsets) of a list of `bytes`; a pair of arrays passes through."""
+    if isinstance(texts, tuple):
+        data, offsets = texts
+        return (np.ascontiguousarray(data, dtype=np.uint8),
+                np.ascontiguousarray(offsets, dtype=np.uint64))
+    offsets = np.zeros(len(texts) + 1, np.uint64)
+    if texts:
+        np.cumsum([len(t) for t in texts], out=offsets[1:])
+    return np.frombuffer(b"".join(texts), dtype=np.uint8), offsets
+
+
+def normalize_text_batch(stages, texts, semantics: int = FST_SEM_LAZY, devices=None,
+                         shards: int = 0, device: int = -1) -> TextResult:
+    """Byte strings in, byte strings out (fst_normalize_text_batch): every string is compiled
+    (label = byte + 1), run through `stages` (one Fst or a list: tagger -> verbalizer ...) and
+    its 1-best output tape printed, all on the device.  `texts`: a list of `bytes`, or a
+    (uint8 array, uint64 offsets) pair."""
+    stages = [stages] if isinstance(stages, Fst) else list(stages)
+    data, offsets = text_csr(texts)
+    hs = (C.c_uint64 * max(len(stages), 1))(*[s.h for s in stages])
+    opts = batch_options(device, semantics, devices, shards)
+    res = FstTextResult()
+    rc = lib().fst_normalize_text_batch(hs, len(stages), data.ctypes.data, offsets.ctypes.data,
+                                        len(offsets) - 1, C.byref(opts), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_normalize_text_batch failed: {rc}")
+    return _take_text(res)
+
+
+def batch_result_to_text(r: BatchResult) -> TextResult:
+    """The host conversion of a label result (fst_batch_result_to_text): what
+    normalize_text_batch returns for the same paths; runs without a GPU."""
+    status = np.ascontiguousarray(r.status, dtype=np.int32)
+    offsets = np.ascontiguousarray(r.offsets, dtype=np.uint64)
+    ilabels = np.ascontiguousarray(r.ilabels, dtype=np.uint32)
+    olabels = np.ascontiguousarray(r.olabels, dtype=np.uint32)
+    weights = np.ascontiguousarray(r.weights, dtype=np.float64)
+    finals = np.ascontiguousarray(r.finals, dtype=np.float64)
+
+    def ptr(a, ct):
+        return C.cast(a.ctypes.data, C.POINTER(ct))
+
+    src = FstBatchResult(len(status), ptr(status, C.c_int32), ptr(offsets, C.c_uint64),
+                         ptr(ilabels, C.c_uint32), ptr(olabels, C.c_uint32),
+                         ptr(weights, C.c_double), ptr(finals, C.c_double),
+                         int(offsets[-1]) if len(offsets) else 0)
+    res = FstTextResult()
+    rc = lib().fst_batch_result_to_text(C.byref(src), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_batch_result_to_text failed: {rc}")
+    return _take_text(res)
 
 
 def coalescer_state(device: int = 0):
