@@ -177,9 +177,18 @@ typedef struct {
  * *out is zeroed once they are checked); num_strings == 0 gives an empty OK result.
  * Semantics, device and FST_BATCH_DEVICES sharding from opts, as for the label entries
  * (shards balanced by fst_chain_cost of stage 1; the result is in input order and
- * byte-identical to a one-shard run).  Each shard uploads bytes and offsets, widens them to
- * labels on the device, runs the stages, emits the text on the device and downloads only the
- * four result arrays.  The result lives in pooled pinned blocks until fst_text_result_free. */
+ * byte-identical to a one-shard run).  Two routes, same result:
+ *   - streamed (one stage whose rhs has no input epsilon and starts with a pull tier, as
+ *     the streamed route of fst_compose_frozen_shortest_path_batch; FSTAMD_STREAM=0 turns it
+ *     off): each shard uploads its bytes in a few parts under the pull kernels, which read
+ *     the bytes themselves (label = byte + 1) and write every finished string's text
+ *     straight into its fixed slot of the pinned result (its own input byte range: no path
+ *     is longer than its input); 20 B per string come down, short slots are closed up on
+ *     the host;
+ *   - sharded (everything else): each shard uploads bytes and offsets, widens them to
+ *     labels on the device, runs the stages, emits the text on the device and downloads
+ *     only the four result arrays.
+ * The result lives in pooled pinned blocks until fst_text_result_free. */
 FstError fst_normalize_text_batch(const FstHandle* stages, uint32_t num_stages,
                                   const uint8_t* text, const uint64_t* offsets,
                                   uint32_t num_strings, const FstBatchOptions* opts,
@@ -258,6 +267,17 @@ int32_t fst_weight_type(FstHandle b);
  * (leader slots in use, calls waiting in its queue).  Both are 0 when no call is in
  * flight; tests check that no slot leaks.  Returns -1 for a negative device. */
 int32_t fst_debug_coalescer_state(int32_t device, uint32_t* queued);
+
+/* Diagnostics / tests, no GPU needed: the host step that closes the streamed text route's
+ * fixed slots up into the CSR result.  In: offsets[0 .. num_strings] = the slots (string i's
+ * bytes start at offsets[i], its slot ends at offsets[i + 1]), nbytes[i] = bytes the device
+ * wrote there (0xFFFFFFFF: the path has an olabel above 256), status[i].  Out: offsets = the
+ * CSR offsets, text compacted in place moving left in input order, status[i] =
+ * FST_PATH_UNSUPPORTED for the 0xFFFFFFFF strings (FST_PATH_INTERNAL should a count exceed
+ * its slot), total_weight[i] = +inf for every non-OK string.  Returns the total bytes.
+ * Nothing at or past offsets[num_strings] is read or written. */
+uint64_t fst_debug_text_compact(uint32_t num_strings, uint64_t* offsets, const uint32_t* nbytes,
+                                int32_t* status, double* total_weight, uint8_t* text);
 
 #ifdef __cplusplus
 }

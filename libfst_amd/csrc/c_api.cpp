@@ -1112,9 +1112,60 @@ struct StreamShard {
   uint32_t launches = 0;
 };
 
-FstError stream_shard(StreamShard& S, DeviceFst& D, const uint32_t* src, const uint64_t* poff,
-                      uint32_t max_len, uint32_t n, int semantics, FstBatchResult* out,
-                      int32_t* first_all, std::mutex* later_mu) {
+// What a streamed batch reads and writes.
+//   label mode (fst_compose_frozen_shortest_path_batch): 4-B labels up; each finished path's
+//     olabels and weights written into the result by the pull tier (copy_out_paths), the
+//     ilabels staged by host threads.
+//   text mode (fst_normalize_text_batch): the bytes up as they are -- the pull tiers read
+//     them (ChainInput::text; no widen kernel and no 4-B label buffer on the way: a widen per
+//     part would queue for CU slots behind the other engine's persistent kernel, as fills
+//     and blits did) -- and each finished path's text written into its fixed text slot
+//     [poff[i], poff[i + 1]) of the result by the chase epilogue (emit_text_paths): with no
+//     input epsilon in the rhs a path has as many arcs as its string has bytes and every arc
+//     emits at most one.  Per string 20 B come down (status, byte count, total weight, the
+//     pull tier's status); no ilabel staging.  The slots are global byte offsets, so the
+//     shards of a call write one result and a single host compaction (text_compact) follows.
+struct StreamIo {
+  const uint32_t* labels = nullptr;  // label mode: the batch's labels from its first one
+  FstBatchResult* out = nullptr;
+  const uint8_t* text = nullptr;     // text mode: the batch's bytes from its first one
+  FstTextResult* tout = nullptr;
+  uint32_t* nbytes = nullptr;        // text mode: [num] (pinned) bytes the device wrote
+  bool text_mode() const { return tout != nullptr; }
+};
+
+// The streamed text batch's last step, on the host: the fixed text slots closed up into the
+// CSR result, moving left in input order (as the label route drops the slots of strings
+// without a path).  In: offsets = the slots, nbytes[i] = what the device wrote into slot i
+// (kTextNotBytes: a path with an olabel > 256), status.  Out: offsets = the prefix sum of the
+// OK strings' byte counts, the text compacted in place; UNSUPPORTED for the kTextNotBytes
+// strings, +inf total weight and no bytes for every non-OK string.  A count beyond its slot
+// (an engine bug) reads INTERNAL and moves nothing.  Returns the total.
+uint64_t text_compact(uint32_t num, uint64_t* offsets, const uint32_t* nbytes, int32_t* status,
+                      double* total_weight, uint8_t* text) {
+  uint64_t dst = 0;
+  for (uint32_t i = 0; i < num; ++i) {
+    const uint64_t a = offsets[i], cap = offsets[i + 1] - a;
+    offsets[i] = dst;
+    if (status[i] == kPathOk && nbytes[i] == kTextNotBytes) status[i] = kPathUnsupported;
+    if (status[i] == kPathOk && nbytes[i] > cap) status[i] = kPathInternal;
+    if (status[i] != kPathOk) {
+      total_weight[i] = w_zero();
+      continue;
+    }
+    const uint64_t nb = nbytes[i];
+    if (dst != a && nb) std::memmove(text + dst, text + a, nb);
+    dst += nb;
+  }
+  offsets[num] = dst;
+  return dst;
+}
+
+FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const uint64_t* poff,
+                      uint32_t max_len, uint32_t n, int semantics, int32_t* first_all,
+                      std::mutex* later_mu) {
+  const bool tm = io.text_mode();
+  FstBatchResult* const out = io.out;  // (label mode)
   // the later tiers of the shards of one device run one shard at a time, each to the end of
   // its leases (declared after this lock, so released before it): the heavy replays size
   // their workspaces from the free HBM, which a concurrent shard's would have taken
@@ -1134,8 +1185,9 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const uint32_t* src, const u
     for (uint32_t i = 0; i <= num; ++i) loff_own[i] = poff[S.s0 + i] - lbase;
     loff = loff_own.data();
   }
-  const uint32_t* lsrc = src ? src + lbase : nullptr;
-  uint32_t* const il_out = out->ilabels + lbase;
+  const uint32_t* lsrc = io.labels ? io.labels + lbase : nullptr;
+  const uint8_t* tsrc = io.text ? io.text + lbase : nullptr;
+  uint32_t* const il_out = tm ? nullptr : out->ilabels + lbase;
   struct Threads {  // joined on every return (declared after what they use)
     std::vector<std::thread> th;
     void join() {
@@ -1178,10 +1230,25 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const uint32_t* src, const u
   DeviceEngine::Lease EB;
   if (parts > 1) EB = DeviceEngine::try_acquire(dev);  // (none free: one engine in order)
   const hipStream_t sA = EA.stream(), sB = EB ? EB.stream() : nullptr;
-  DevBuf d_lab(std::max<uint64_t>(total, 1) * 4), d_off((num + 1) * 8ull),
+  // (text mode: d_lab holds the bytes themselves)
+  DevBuf d_lab(std::max<uint64_t>(total, 1) * (tm ? 1 : 4)), d_off((num + 1) * 8ull),
       d_first(std::max<size_t>(num, 1) * 4ull), d_ctr(64 * 4);  // item counter per part
   DevOut o(num, total + 4);
   if (!d_lab.p || !d_off.p || !d_first.p || !d_ctr.p || !o.ok()) return FST_OOM;
+  // text mode: byte counts and total weights per string, and one TextOutDev per part (the
+  // kernels reach it through BatchOutDev::text), uploaded with the offsets
+  // (d_lab4: the widened labels of a shard that hands strings on, allocated only then)
+  std::unique_ptr<DevBuf> d_nb, d_tw, d_tx, d_lab4;
+  std::vector<TextOutDev> txs;  // (outlives the streams' work: declared before sync_all)
+  if (tm) {
+    d_nb = std::make_unique<DevBuf>(std::max<size_t>(num, 1) * 4ull);
+    d_tw = std::make_unique<DevBuf>(std::max<size_t>(num, 1) * 8ull);
+    d_tx = std::make_unique<DevBuf>(64 * sizeof(TextOutDev));
+    if (!d_nb->p || !d_tw->p || !d_tx->p) return FST_OOM;
+    for (size_t p = 0; p < parts; ++p)
+      txs.push_back(TextOutDev{io.tout->text + lbase, (uint32_t*)d_nb->p + cut[p],
+                               (double*)d_tw->p + cut[p]});
+  }
   // the arena's path arrays shifted so that each element shares its host twin's address
   // modulo 16 (the copy-out's 16-B units, kernels/device_common.hpp copy_out_paths)
   BatchOutDev vb = o.v;
@@ -1218,11 +1285,16 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const uint32_t* src, const u
               hipMemsetD32Async((hipDeviceptr_t)d_first.p, kPathInternal, num, up) == hipSuccess &&
               hipMemsetAsync(d_ctr.p, 0, 64 * 4, up) == hipSuccess &&
               hipMemcpyAsync(d_off.p, loff, (num + 1) * 8ull, hipMemcpyHostToDevice, up) ==
-                  hipSuccess;
+                  hipSuccess &&
+              (!tm || hipMemcpyAsync(d_tx->p, txs.data(), parts * sizeof(TextOutDev),
+                                     hipMemcpyHostToDevice, up) == hipSuccess);
     constexpr uint64_t kChunk = 1ull << 21;  // labels per staged chunk (8 MB)
     for (size_t p = 0; p < parts && ok; ++p) {
       const uint64_t a = loff[cut[p]], z = loff[cut[p + 1]];
-      if (stage_mode == 1) {
+      if (tm) {  // the part's bytes, as they are
+        ok = z == a || hipMemcpyAsync((uint8_t*)d_lab.p + a, tsrc + a, z - a,
+                                      hipMemcpyHostToDevice, up) == hipSuccess;
+      } else if (stage_mode == 1) {
         for (uint64_t c = a; c < z && ok; c += kChunk) {
           const uint64_t e = std::min(z, c + kChunk), w = e - c;
           const uint64_t T = w >= (1u << 19) ? 4 : 1;
@@ -1251,7 +1323,7 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const uint32_t* src, const u
     if (!ok) R.failed = true;
     R.cv.notify_all();
   });
-  if (stage_mode != 1) {
+  if (!tm && stage_mode != 1) {
     // the result's ilabels, once the uploads are staged: the runtime's staging copies of
     // a pageable source read the same pages, and the kernels wait for them, not for these
     const uint64_t T = total >= (1u << 20) ? 3 : 1;
@@ -1287,22 +1359,28 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const uint32_t* src, const u
       }
       const uint32_t s0 = cut[p], np = cut[p + 1] - cut[p];
       ChainInput in{(const uint32_t*)d_lab.p, (const uint64_t*)d_off.p + s0, np, max_len};
+      if (tm) in.text = (const uint8_t*)d_lab.p;  // (the bytes, in the labels' place)
       BatchOutDev v = vb;
       v.status += s0;
       v.path_len += s0;
       v.path_off += s0;
       v.final_w += s0;
       v.slots = (const uint64_t*)d_off.p + s0;
-      v.host_ol = out->olabels + lbase;
-      v.host_w = out->weights + lbase;
-      if (ab_nocopy) v.host_ol = nullptr, v.host_w = nullptr;
+      if (tm) {
+        v.text = (const TextOutDev*)d_tx->p + p;
+      } else {
+        v.host_ol = out->olabels + lbase;
+        v.host_w = out->weights + lbase;
+      }
+      // (label mode only: without its emission the text route has no result at all)
+      if (ab_nocopy && !tm) v.host_ol = nullptr, v.host_w = nullptr;
       v.first_status = (int32_t*)d_first.p + s0;
       // the pull tier alone: no fill, copy or host synchronisation between parts (a fill
       // or copy is a blit kernel that waits for CU slots behind the other engine's
       // persistent kernel, and had held this engine's next part back); the later tiers
       // and the downloads come after the last part
       if (hipStreamWaitEvent(s, K->ev[p], 0) != hipSuccess ||
-          E->launch_pull_part(D, in, n, semantics, v, s, (unsigned int*)d_ctr.p + p) !=
+          E->launch_pull_part(D, in, n, semantics, v, s, (unsigned int*)d_ctr.p + p, tm) !=
               hipSuccess) {
         perr[p] = FST_OOM;
         return;
@@ -1320,15 +1398,19 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const uint32_t* src, const u
     if (x && hipStreamSynchronize(x) != hipSuccess) return FST_OOM;
   for (size_t p = 0; p < parts; ++p)
     if (perr[p] != FST_OK) return perr[p];
-  int32_t* const st_out = out->status + S.s0;
-  double* const fin_out = out->final_weights + S.s0;
+  int32_t* const st_out = (tm ? io.tout->status : out->status) + S.s0;
+  // (text mode: the total weights in the final weights' place, and the byte counts)
+  double* const fin_out = (tm ? io.tout->total_weight : out->final_weights) + S.s0;
+  const void* const d_fin = tm ? d_tw->p : o.fin.p;
   int32_t* const first = first_all + S.s0;
   // statuses, final weights and the pull tier's statuses in one download each
   auto download = [&](bool with_first) {
     return (hipMemcpyAsync(st_out, o.status.p, num * 4ull, hipMemcpyDeviceToHost, sA) ==
                 hipSuccess &&
-            hipMemcpyAsync(fin_out, o.fin.p, num * 8ull, hipMemcpyDeviceToHost, sA) ==
+            hipMemcpyAsync(fin_out, d_fin, num * 8ull, hipMemcpyDeviceToHost, sA) ==
                 hipSuccess &&
+            (!tm || hipMemcpyAsync(io.nbytes + S.s0, d_nb->p, num * 4ull, hipMemcpyDeviceToHost,
+                                   sA) == hipSuccess) &&
             (!with_first || hipMemcpyAsync(first, d_first.p, num * 4ull, hipMemcpyDeviceToHost,
                                            sA) == hipSuccess) &&
             hipStreamSynchronize(sA) == hipSuccess);
@@ -1340,21 +1422,44 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const uint32_t* src, const u
   bool handed = false;
   for (uint32_t i = 0; i < num && !handed; ++i) handed = first[i] != kPathOk && first[i] != kPathEmpty;
   uint32_t launches = (uint32_t)parts;
+  if (tm && std::getenv("FSTAMD_SHARD_LOG")) {  // tests (text mode): what the pull tier handed on
+    uint32_t nh = 0;
+    for (uint32_t i = 0; i < num; ++i) nh += first[i] != kPathOk && first[i] != kPathEmpty;
+    std::fprintf(stderr, "[libfst_amd stream] dev %d strings %u..%u parts %zu handed-on %u\n", dev,
+                 S.s0, S.s1, parts, nh);
+  }
   if (handed) {
     later_lock.lock();
     ChainInput in{(const uint32_t*)d_lab.p, (const uint64_t*)d_off.p, num, max_len};
+    // text mode: the later tiers read 4-B labels -- the shard's bytes widened once, now
+    // (only batches that hand strings on pay for the buffer and the kernel)
+    if (tm) {
+      d_lab4 = std::make_unique<DevBuf>(std::max<uint64_t>(total, 1) * 4);
+      if (!d_lab4->p ||
+          EA->widen_text((const uint8_t*)d_lab.p, (const uint64_t*)d_off.p, num,
+                         (uint32_t*)d_lab4->p, sA) != hipSuccess)
+        return FST_OOM;
+      in.labels = (const uint32_t*)d_lab4->p;
+    }
     BatchOutDev v = vb;
     v.slots = (const uint64_t*)d_off.p;
     EA->set_after_pull(true);
-    const hipError_t e = EA->run_chain(D, in, n, semantics, v, sA, nullptr);
+    hipError_t e = EA->run_chain(D, in, n, semantics, v, sA, nullptr);
     EA->set_after_pull(false);
+    // text mode: the paths the later tiers left in the arena's slots, emitted as the pull
+    // tier's are (the same slots of the result)
+    if (tm && e == hipSuccess)
+      e = EA->text_fixup(v, TextOutDev{io.tout->text + lbase, (uint32_t*)d_nb->p,
+                                       (double*)d_tw->p},
+                         (const int32_t*)d_first.p, num, sA);
     if (e != hipSuccess || !download(false)) return FST_OOM;
     ++launches;
   }
 
   // ---- paths the later tiers wrote (device arena, same slots) ----
   uint64_t nfix = 0;
-  for (uint32_t i = 0; i < num; ++i) nfix += st_out[i] == kPathOk && first[i] != kPathOk;
+  if (!tm)
+    for (uint32_t i = 0; i < num; ++i) nfix += st_out[i] == kPathOk && first[i] != kPathOk;
   if (nfix) {
     const auto d2h = [&](void* dst, const void* s, size_t bytes) {
       return bytes == 0 || hipMemcpyAsync(dst, s, bytes, hipMemcpyDeviceToHost, sA) == hipSuccess;
@@ -1387,9 +1492,14 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const uint32_t* src, const u
 // slice of it (fixed slots: no compaction between shards, no gather), then strings without
 // a path are compacted out on the host.  Shards are contiguous string ranges of equal
 // estimated cost (FrozenFst::chain_cost), as in run_sharded.
-int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b,
-                 const uint32_t* labels, const uint64_t* offsets, uint32_t num, uint32_t n,
-                 int semantics, FstBatchResult* out) {
+// `io`: the mode (StreamIo) with the caller's labels or bytes (indexed by `offsets`) and its
+// result.  Text mode: the text result is allocated with one byte per input byte (the slots),
+// the shards emit into it, and text_compact closes the short slots up.
+bool alloc_text_result(FstTextResult* out, uint32_t num, uint64_t tot);
+int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b, StreamIo io,
+                 const uint64_t* offsets, uint32_t num, uint32_t n, int semantics) {
+  const bool tm = io.text_mode();
+  FstBatchResult* const out = io.out;  // (label mode)
   DeviceRestore_ restore;
   std::vector<DeviceFst*> Ds(devices.size(), nullptr);
   for (size_t d = 0; d < devices.size(); ++d) {  // (the rhs goes to every device first)
@@ -1400,17 +1510,31 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b,
       return kStreamNotApplicable;
   }
   const uint64_t base0 = offsets[0], total = offsets[num] - base0;
-  if (!alloc_result(out, num, total)) return FST_OOM;
-  if (!pin_is_pinned(out->ilabels) || !pin_is_pinned(out->olabels) ||
-      !pin_is_pinned(out->weights) || !pin_is_pinned(out->path_offsets) ||
-      !pin_is_pinned(out->status) || !pin_is_pinned(out->final_weights)) {
-    fst_batch_result_free(out);
-    return kStreamNotApplicable;
+  if (tm) {
+    FstTextResult* const t = io.tout;
+    if (!alloc_text_result(t, num, total)) return FST_OOM;
+    if (!pin_is_pinned(t->status) || !pin_is_pinned(t->text_offsets) ||
+        !pin_is_pinned(t->total_weight) || !pin_is_pinned(t->text)) {
+      fst_text_result_free(t);
+      return kStreamNotApplicable;
+    }
+  } else {
+    if (!alloc_result(out, num, total)) return FST_OOM;
+    if (!pin_is_pinned(out->ilabels) || !pin_is_pinned(out->olabels) ||
+        !pin_is_pinned(out->weights) || !pin_is_pinned(out->path_offsets) ||
+        !pin_is_pinned(out->status) || !pin_is_pinned(out->final_weights)) {
+      fst_batch_result_free(out);
+      return kStreamNotApplicable;
+    }
   }
-  const uint32_t* src = labels ? labels + base0 : nullptr;
+  if (io.labels) io.labels += base0;
+  if (io.text) io.text += base0;
+  PinnedVec<uint32_t> nbytes(tm ? std::max<uint32_t>(num, 1) : 0);
+  io.nbytes = tm ? nbytes.data() : nullptr;
 
-  // ---- the result's CSR offsets (= the rebased input offsets) and max_len ----
-  uint64_t* const poff = out->path_offsets;
+  // ---- the result's CSR offsets (= the rebased input offsets) and max_len; text mode: the
+  // text slots, which text_compact turns into the CSR offsets in the end ----
+  uint64_t* const poff = tm ? io.tout->text_offsets : out->path_offsets;
   uint32_t max_len = 0;
   {
     const uint32_t nt = num >= (1u << 18) ? 4 : 1;
@@ -1465,8 +1589,9 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b,
   }
   if (shard_log)  // tests: the shard plan and the route
     for (uint32_t j = 0; j < nsh; ++j)
-      std::fprintf(stderr, "[libfst_amd shard] %u dev %d strings %u..%u cost %.6g route streamed\n",
-                   j, sh[j].dev, sh[j].s0, sh[j].s1, pre[sh[j].s1] - pre[sh[j].s0]);
+      std::fprintf(stderr, "[libfst_amd shard] %u dev %d strings %u..%u cost %.6g route %s\n", j,
+                   sh[j].dev, sh[j].s0, sh[j].s1, pre[sh[j].s1] - pre[sh[j].s0],
+                   tm ? "streamed-text" : "streamed");
 
   PinnedVec<int32_t> first(std::max<uint32_t>(num, 1));
   std::vector<std::mutex> later_mu(devices.size());  // (stream_shard: per device)
@@ -1476,7 +1601,7 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b,
     auto run = [&](uint32_t j) {
       StreamShard& S = sh[j];
       const size_t d = (size_t)(j % devices.size());
-      S.err = stream_shard(S, *Ds[d], src, poff, max_len, n, semantics, out, first.data(),
+      S.err = stream_shard(S, *Ds[d], io, poff, max_len, n, semantics, first.data(),
                            &later_mu[d]);
     };
     std::vector<std::thread> th;
@@ -1495,6 +1620,15 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b,
   t_last_stats = agg;
   if (t_prof) t_prof->lap(2);
 
+  if (tm) {  // ---- short text slots closed up (in order, moving left) ----
+    FstTextResult* const t = io.tout;
+    t->total_bytes = text_compact(num, poff, io.nbytes, t->status, t->total_weight, t->text);
+    if (t_prof) {
+      t_prof->runs = (int)agg.launches;
+      t_prof->lap(3);
+    }
+    return FST_OK;
+  }
   // ---- strings without a path: their slots dropped (in order, moving left) ----
   uint64_t nbad = 0;
   for (uint32_t i = 0; i < num; ++i) nbad += out->status[i] != kPathOk;
@@ -2444,7 +2578,10 @@ FstError fst_compose_frozen_shortest_path_batch(FstHandle b_handle, const uint32
   if (num_strings > 0) {
     const char* se = std::getenv("FSTAMD_STREAM");
     if (!(se && std::strcmp(se, "0") == 0)) {
-      const int e = run_streamed(devices, nsh, *b, labels, offsets, num_strings, n, semantics, out);
+      StreamIo io;
+      io.labels = labels;
+      io.out = out;
+      const int e = run_streamed(devices, nsh, *b, io, offsets, num_strings, n, semantics);
       if (e != kStreamNotApplicable) {
         if (e != FST_OK) {
           fst_batch_result_free(out);
@@ -2734,6 +2871,26 @@ FstError fst_normalize_text_batch(const FstHandle* stages, uint32_t num_stages,
   struct ProfScope {
     ~ProfScope() { t_prof = nullptr; }
   } prof_scope;
+  // one stage on an rhs without input epsilons and a pull tier first: the streamed text
+  // batch, on one device or sharded over several (FSTAMD_STREAM=0 turns it off)
+  if (num_stages == 1) {
+    const char* se = std::getenv("FSTAMD_STREAM");
+    if (!(se && std::strcmp(se, "0") == 0)) {
+      StreamIo io;
+      io.text = text;
+      io.tout = out;
+      const int e = run_streamed(devices, nsh, *fs[0], io, offsets, num_strings, 1, semantics);
+      if (e != kStreamNotApplicable) {
+        if (e != FST_OK) {
+          fst_text_result_free(out);
+          return (FstError)e;
+        }
+        prof.lap(5);
+        prof.print("fst_normalize_text_batch (streamed)");
+        return FST_OK;
+      }
+    }
+  }
   std::vector<double> cost(nsh > 1 ? num_strings : 0);
   for (size_t i = 0; i < cost.size(); ++i) cost[i] = fs[0]->chain_cost(offsets[i + 1] - offsets[i]);
   const ShardSink sink{
@@ -2970,6 +3127,12 @@ int32_t fst_debug_coalescer_state(int32_t device, uint32_t* queued) {
   std::lock_guard<std::mutex> g(C.mu);
   if (queued) *queued = (uint32_t)C.q.size();
   return C.leaders;
+}
+
+uint64_t fst_debug_text_compact(uint32_t num_strings, uint64_t* offsets, const uint32_t* nbytes,
+                                int32_t* status, double* total_weight, uint8_t* text) {
+  if (!offsets || (num_strings && (!nbytes || !status || !total_weight))) return 0;
+  return text_compact(num_strings, offsets, nbytes, status, total_weight, text);
 }
 
 int32_t fst_weight_type(FstHandle b) {

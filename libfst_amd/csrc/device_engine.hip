@@ -717,6 +717,9 @@ hipError_t DeviceEngine::run_chain(const DeviceFst& rhs, const ChainInput& in, u
   HIP_TRY(hipSetDevice(dev_));
   // the pull tiers alone copy paths out to the host (they must come first)
   if (out.host_ol && !pull_first(rhs, semantics)) return hipErrorInvalidValue;
+  // host_w goes with host_ol: alone it would be BatchOutDev::text, which is launch_pull_part's
+  // (the streamed text batch) -- the tiers here read 4-B labels and emit no text
+  if (out.host_w && !out.host_ol) return hipErrorInvalidValue;
   unsigned int* counter = (unsigned int*)scratch(kCounter, kCounterBytes);
   if (!counter) return hipErrorOutOfMemory;
   HIP_TRY(hipMemsetAsync(counter, 0, 64, stream));
@@ -1350,22 +1353,35 @@ hipError_t DeviceEngine::run_lazy_pull(const DeviceFst& rhs, const ChainInput& i
 
 hipError_t DeviceEngine::launch_pull_part(const DeviceFst& rhs, const ChainInput& in,
                                           uint32_t n, int semantics, const BatchOutDev& out,
-                                          hipStream_t stream, unsigned int* item_ctr) {
+                                          hipStream_t stream, unsigned int* item_ctr, bool text) {
   HIP_TRY(hipSetDevice(dev_));
   if (!pull_first(rhs, semantics)) return hipErrorInvalidValue;
+  // text: the text emission writes each string's fixed slot, and there is no path copy-out.
+  // Labels: host_w goes with host_ol (alone it would be read as BatchOutDev::text)
+  if (text ? (!out.text || !out.slots || out.host_ol) : (out.host_w && !out.host_ol))
+    return hipErrorInvalidValue;
+  if (!in.labels) return hipErrorInvalidValue;  // (or the bytes: the same place)
   if (in.num_strings == 0) return hipSuccess;
   const bool lazy = semantics != 1;
-  const int per_cu = lazy ? lazy_pull_waves_per_cu(rhs, in.max_len) : pull_waves_per_cu(rhs, in.max_len);
+  const int per_cu = text   ? text_pull_waves_per_cu(rhs, in.max_len, lazy)
+                     : lazy ? lazy_pull_waves_per_cu(rhs, in.max_len)
+                            : pull_waves_per_cu(rhs, in.max_len);
   const uint32_t back_cap =
       (uint32_t)std::min<uint64_t>((uint64_t)(in.max_len + 1) * kPullW, 1u << 22);
   // the back slabs sized for a full grid whatever this part's size, so no later part
   // reallocates them (a free waits for the device) while an earlier one runs
   uint32_t full = (uint32_t)std::max<uint64_t>((uint64_t)per_cu * num_cus_, 1);
+  // (tests of the text batch: a few waves take every string, so every emission runs with
+  // jobs pending; the label batch's parts take no such cap, as before)
+  if (text) full = std::min<uint32_t>(full, grid_cap(lazy ? "FSTAMD_LP_GRID" : "FSTAMD_P_GRID"));
   while (full > 1 && (uint64_t)full * kChaseBatch * back_cap * 8 > (24ull << 30)) full /= 2;
   uint2* back = (uint2*)scratch(lazy ? kLpBack : kPullBack, (size_t)full * kChaseBatch * back_cap * 8);
   if (!back) return hipErrorOutOfMemory;
   const uint32_t grid = std::max<uint32_t>(std::min<uint32_t>(full, in.num_strings), 1);
   EagerLaunch lp{nullptr, nullptr, in.num_strings, nullptr, 0, 0, back, back_cap, watchdog_ticks()};
+  if (text)
+    return lazy ? launch_lazy_pull_text(rhs, in, n, item_ctr, lp, out, grid, stream)
+                : launch_eager_pull_text(rhs, in, n, item_ctr, lp, out, grid, stream);
   return lazy ? launch_lazy_pull(rhs, in, n, item_ctr, lp, out, grid, stream)
               : launch_eager_pull(rhs, in, n, item_ctr, lp, out, grid, stream);
 }
@@ -2590,6 +2606,16 @@ hipError_t DeviceEngine::text_write(const BatchOutDev& s, uint32_t num, const in
   if (!num) return hipSuccess;
   const uint32_t grid = std::min<uint32_t>(num, (uint32_t)num_cus_ * 32);
   text_write_kernel<<<grid, 64, 0, stream>>>(s, num, status, offsets, text, cap);
+  return hipGetLastError();
+}
+
+hipError_t DeviceEngine::text_fixup(const BatchOutDev& s, const TextOutDev& tx,
+                                    const int32_t* first, uint32_t num, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(dev_));
+  if (!num) return hipSuccess;
+  if (!s.slots || !first) return hipErrorInvalidValue;
+  const uint32_t grid = std::min<uint32_t>(num, (uint32_t)num_cus_ * 32);
+  text_fixup_kernel<<<grid, 64, 0, stream>>>(s, tx, first, num);
   return hipGetLastError();
 }
 

@@ -213,15 +213,44 @@ struct BatchOutDev {
   //     chase skips the ilabels (the host stages them: on an OK path il[k] = label k).
   const uint64_t* slots = nullptr;
   uint32_t* host_ol = nullptr;
-  double* host_w = nullptr;
+  // (host_w is dead in the streamed text batch, which has no host_ol: `text`, below, shares
+  // its place, so the kernels' argument block does not grow -- DESIGN.md §3.1: the layout of
+  // the argument structs steers the pull tiers' register allocation)
+  union {
+    double* host_w = nullptr;
+    const struct TextOutDev* text;
+  };
   // (host side, not read by kernels) when set, run_chain copies the statuses right after
   // the first tier here: which strings the pull tier finished (and copied out) itself
   int32_t* first_status = nullptr;
+  // The streamed text batch (c_api.cpp, text mode of run_streamed; launch_pull_part with
+  // text = true, `slots` set, host_ol null): after each batched chase the wave emits the
+  // finished paths as text (kernels/device_common.hpp emit_text_paths).  One pointer to a
+  // small device struct, not three fields.  Only the pull tiers' text instances read it;
+  // every other caller leaves the place to host_w, which goes with host_ol.
+};
+
+// Text outputs of the streamed text batch.  String si's bytes go to its fixed text slot
+// host_text[slots[si] ..]: its own input byte range (no input epsilon in the rhs: a path of
+// a string of L bytes has L arcs and every arc emits at most one byte).
+constexpr uint32_t kTextNotBytes = 0xFFFFFFFFu;
+struct TextOutDev {
+  uint8_t* host_text;  // host-mapped result bytes, indexed like the arena (BatchOutDev::slots)
+  uint32_t* nbytes;    // [num] device: bytes written, kTextNotBytes for a path with an
+                       // olabel > 256 (the host reports UNSUPPORTED; the device status stays
+                       // OK: the later tiers take every UNSUPPORTED string for theirs)
+  double* total_w;     // [num] device: the serial fold of the path's weights and the final
 };
 
 // Chain inputs (batch API) or one general lhs FST (single-call C ABI).
 struct ChainInput {
-  const uint32_t* labels;
+  // 4-B labels, or -- the streamed text batch alone (launch_pull_part with text = true: the
+  // pull tiers' text instances, text_pull.hip) -- the strings as bytes, label = byte + 1.
+  // One place for both, so the struct (a kernel argument) is the same for every kernel.
+  union {
+    const uint32_t* labels;
+    const uint8_t* text;
+  };
   const uint64_t* offsets;
   uint32_t num_strings;
   uint32_t max_len;
@@ -302,6 +331,16 @@ bool pull_f32(const DeviceFst& rhs, uint32_t max_len);
 hipError_t launch_eager_pull(const DeviceFst& rhs, const ChainInput& in, uint32_t n_best,
                              unsigned int* next_item, const EagerLaunch& lp,
                              const BatchOutDev& out, uint32_t grid, hipStream_t stream);
+// The streamed text batch's instances of the two pull kernels (text_pull.hip: byte labels,
+// text emission; pull_kernel_dispatch.hpp picks the same variant as for labels): resident
+// waves per CU and the launches.
+int text_pull_waves_per_cu(const DeviceFst& rhs, uint32_t max_len, bool lazy);
+hipError_t launch_eager_pull_text(const DeviceFst& rhs, const ChainInput& in, uint32_t n_best,
+                                  unsigned int* next_item, const EagerLaunch& lp,
+                                  const BatchOutDev& out, uint32_t grid, hipStream_t stream);
+hipError_t launch_lazy_pull_text(const DeviceFst& rhs, const ChainInput& in, uint32_t n_best,
+                                 unsigned int* next_item, const EagerLaunch& lp,
+                                 const BatchOutDev& out, uint32_t grid, hipStream_t stream);
 // Lazy pull tier (eager_pull.hip, kernels/lazy_pull.hpp): resident waves per CU, launch.
 int lazy_pull_waves_per_cu(const DeviceFst& rhs, uint32_t max_len);
 bool lazy_pull_f32(const DeviceFst& rhs, uint32_t max_len);
@@ -374,7 +413,10 @@ class DeviceEngine {
   // then run once over the whole batch: run_chain with set_after_pull(true).
   hipError_t launch_pull_part(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
                               int semantics, const BatchOutDev& out, hipStream_t stream,
-                              unsigned int* item_ctr);
+                              unsigned int* item_ctr, bool text = false);
+  // text = true (the streamed text batch): `in` holds bytes (ChainInput::text), `out` the
+  // text outputs (BatchOutDev::text, with slots and without host_ol), and the pull tier's
+  // text instance runs.  Otherwise host_w without host_ol is refused: it shares text's place.
   // run_chain after launch_pull_part: the statuses are the pull tier's (no INTERNAL fill,
   // no pull launch); the later tiers take the strings it handed on.
   void set_after_pull(bool v) { after_pull_ = v; }
@@ -418,6 +460,11 @@ class DeviceEngine {
   // past `cap` is written.  Asynchronous on `stream`.
   hipError_t text_write(const BatchOutDev& s, uint32_t num, const int32_t* status,
                         const uint64_t* offsets, uint8_t* text, uint64_t cap, hipStream_t stream);
+  // The streamed text batch's strings the pull tier handed on, once the later tiers have
+  // written their paths to the arena's fixed slots: the same emission (emit_text_paths) for
+  // every string whose `first` status is neither OK nor EMPTY.  Asynchronous on `stream`.
+  hipError_t text_fixup(const BatchOutDev& s, const TextOutDev& tx, const int32_t* first,
+                        uint32_t num, hipStream_t stream);
   // fail[i] = st[i] where fail[i] is still OK (the first failing stage wins).
   hipError_t merge_status(int32_t* fail, const int32_t* st, uint32_t num, hipStream_t stream);
   // fst_shortest_path on an explicit graph; `g` holds the FST itself (CSR, arcs in

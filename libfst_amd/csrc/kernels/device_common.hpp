@@ -136,6 +136,66 @@ __device__ __forceinline__ void copy_out_paths(const BatchOutDev& out, uint32_t 
 }
 #endif
 
+// Streamed text batches (BatchOutDev::text), in copy_out_paths' place: after a batched chase
+// (or, for the strings the later tiers finished, from text_fixup_kernel with one job) lane j
+// < njobs holds job j -- string my_si, arena slot my_o, my_L arcs, final weight my_fw -- and
+// the wave turns the paths it finds at those slots into text:
+//   weight : lane j folds job j's weights in path order, ((0 + w_1) + .. + w_L) + final: the
+//            reference's own sum (kernels/text_io.hpp), all jobs at once, L dependent adds.
+//            No lane-crossing tree: it would round differently.
+//   bytes  : one job at a time, 64 arcs per pass: a coalesced olabel load, the ballot of the
+//            non-epsilon lanes, each such lane's rank among them plus the running base of the
+//            earlier passes; the byte olabel - 1 goes to text slot + base + rank on its own
+//            (neighbouring strings share dwords).  The text slot is the string's arena slot
+//            (its own input byte range), and no byte is written at or past slot + L.
+//   an olabel > 256 is no byte: nbytes = kTextNotBytes (what an earlier pass already stored
+//            stays inside the string's own slot and is dropped with it).
+// The chase's stores come from lanes of this same wave: the fence is copy_out_paths'.
+__device__ __forceinline__ void emit_text_paths(const BatchOutDev& out, const TextOutDev tx,
+                                                uint32_t njobs, uint32_t my_si, uint64_t my_o,
+                                                uint32_t my_L, double my_fw, uint32_t lane,
+                                                uint32_t num_strings) {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  const bool mine = lane < njobs;
+  const uint32_t maxL =
+      __builtin_amdgcn_readfirstlane(__ockl_wfred_max_u32(mine ? my_L : 0u));
+  double d = w_one();
+  for (uint32_t k0 = 0; k0 < maxL; k0 += 4) {  // uniform trip count; four loads in flight
+    double w[4];
+#pragma unroll
+    for (uint32_t u = 0; u < 4; ++u)
+      w[u] = mine && k0 + u < my_L ? out.out_w[FB(my_o + k0 + u, out.arc_cap, 240)] : 0.0;
+#pragma unroll
+    for (uint32_t u = 0; u < 4; ++u)
+      if (mine && k0 + u < my_L) d = w_times(d, w[u]);
+  }
+  uint32_t my_n = 0;
+  for (uint32_t j = 0; j < njobs; ++j) {  // uniform
+    const uint32_t Lj = __builtin_amdgcn_readlane(my_L, j);
+    const uint64_t oj = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(my_o >> 32), j) << 32) |
+                        (uint32_t)__builtin_amdgcn_readlane((uint32_t)my_o, j);
+    uint8_t* const dst = tx.host_text + oj;
+    uint32_t base = 0;
+    bool bad = false;
+    for (uint32_t k0 = 0; k0 < Lj; k0 += 64) {
+      const uint32_t k = k0 + lane;
+      const uint32_t ol = k < Lj ? out.out_ol[FB(oj + k, out.arc_cap, 241)] : kEpsilon;
+      const bool nz = ol != kEpsilon;
+      bad |= __ballot(ol > 256u) != 0;
+      const unsigned long long mask = __ballot(nz);
+      const uint32_t rank = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+      if (nz && rank < Lj)
+        __builtin_nontemporal_store((uint8_t)(ol - 1u), dst + FB(rank, Lj, 242));
+      base += (uint32_t)__popcll(mask);
+    }
+    if (lane == j) my_n = bad ? kTextNotBytes : base;
+  }
+  if (mine) {
+    tx.nbytes[FB(my_si, num_strings, 243)] = my_n;
+    tx.total_w[FB(my_si, num_strings, 244)] = my_n == kTextNotBytes ? w_zero() : w_times(d, my_fw);
+  }
+}
+
 // Fst.arcsByIlabel (src/fst.zig:112-136): global arc range [lo, hi) of the arcs of
 // state `s` whose ilabel == label.  Spans of <= 8 arcs are counted with independent
 // loads (no dependent binary-search chain); longer spans use the two binary searches.

@@ -282,7 +282,11 @@ __device__ __forceinline__ void pull_group(const RevView& rv, uint32_t lab, uint
 // max_len * max weight < 2^24), where every f32 sum, min and compare equals the f64 one.
 // Strings longer than in.max_len (a caller's wrong bound) are handed on, so the bound
 // always holds.  RK 6: RK 3 with packed (distance, key) cells (PullLdsPacked above).
-template <int EW, int KP, bool DIRECT, int WAVES_PER_EU, int RK = 0>
+// TEXT (the streamed text batch, text_pull.hip): the strings are bytes (ChainInput::text,
+// label = byte + 1) and every batched chase ends with the text emission (BatchOutDev::text,
+// emit_text_paths) instead of the path copy-out; no ilabels are written.  A compile-time
+// axis in a translation unit of its own: the label instances' code is untouched by it.
+template <int EW, int KP, bool DIRECT, int WAVES_PER_EU, int RK = 0, bool TEXT = false>
 __global__ void __launch_bounds__(64, WAVES_PER_EU)
 eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
                   unsigned int* next_item, EagerLaunch lp, BatchOutDev out) {
@@ -365,7 +369,8 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
           b = FB(sl[FB(id, lp.back_cap, 60)], rv.nrec, 63);
         }
         const uint2 h = hdr[k];
-        if (!out.host_ol) out.out_il[jb.o + k] = in.labels[jb.off + k];
+        if constexpr (!TEXT)
+          if (!out.host_ol) out.out_il[jb.o + k] = in.labels[jb.off + k];
         uint32_t src8;
         if constexpr (PACK) {
           const uint32_t r = rpk[b];
@@ -412,7 +417,9 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         out.work[2 * jb.si + 1] = jb.relax;
       }
     }
-    if (out.host_ol) copy_out_paths(out, njobs, jb.o, jb.L, lane);
+    if constexpr (TEXT)
+      emit_text_paths(out, *out.text, njobs, jb.si, jb.o, jb.L, jb.fw, lane, in.num_strings);
+    else if (out.host_ol) copy_out_paths(out, njobs, jb.o, jb.L, lane);
     njobs = 0;
     wave_lds_sync();
   };
@@ -477,6 +484,9 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         fail = kPathInternal;
         break;
       }
+      if constexpr (TEXT) {
+        if ((k & 63u) == 0) labs = k + lane < L ? in.text[off + k + lane] + 1u : 0u;
+      } else
       if ((k & 63u) == 0) labs = k + lane < L ? in.labels[off + k + lane] : 0u;
       const uint32_t lab = __builtin_amdgcn_readlane(labs, k & 63u);
       if (lab == kEpsilon) {  // lhs epsilon output: not a layered lattice

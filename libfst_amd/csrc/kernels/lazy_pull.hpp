@@ -154,7 +154,9 @@ struct LazyPullLds {
 // target's in-arc group (block x, slot m), as tier P's; the chase walks the states back from
 // the best final's and re-derives each record from its target (block 0 at t * KP, blocks
 // 1.. from rxrec[t].x).  Else 4-B records: the reverse record's index.
-template <int EW, int KP, bool DIRECT, int WAVES_PER_EU, int RK, bool B1 = false>
+// TEXT: as eager_pull_kernel's (the streamed text batch, text_pull.hip).
+template <int EW, int KP, bool DIRECT, int WAVES_PER_EU, int RK, bool B1 = false,
+          bool TEXT = false>
 __global__ void __launch_bounds__(64, WAVES_PER_EU)
 lazy_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
                  unsigned int* next_item, EagerLaunch lp, BatchOutDev out) {
@@ -227,7 +229,8 @@ lazy_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
           b = FB(sl[FB(id, lp.back_cap, 70)], rv.nrec, 73);
         }
         const uint2 h = hdr[k];
-        if (!out.host_ol) out.out_il[jb.o + k] = in.labels[jb.off + k];
+        if constexpr (!TEXT)
+          if (!out.host_ol) out.out_il[jb.o + k] = in.labels[jb.off + k];
         uint32_t src8;
         if constexpr (RK == 2) {
           const uint2 r = rv.rrec8[b];
@@ -260,7 +263,9 @@ lazy_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         out.work[2 * jb.si + 1] = jb.relax;
       }
     }
-    if (out.host_ol) copy_out_paths(out, njobs, jb.o, jb.L, lane);
+    if constexpr (TEXT)
+      emit_text_paths(out, *out.text, njobs, jb.si, jb.o, jb.L, jb.fw, lane, in.num_strings);
+    else if (out.host_ol) copy_out_paths(out, njobs, jb.o, jb.L, lane);
     njobs = 0;
     wave_lds_sync();
   };
@@ -329,6 +334,9 @@ lazy_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         fail = kPathInternal;
         break;
       }
+      if constexpr (TEXT) {
+        if ((k & 63u) == 0) labs = k + lane < L ? in.text[off + k + lane] + 1u : 0u;
+      } else
       if ((k & 63u) == 0) labs = k + lane < L ? in.labels[off + k + lane] : 0u;
       const uint32_t lab = __builtin_amdgcn_readlane(labs, k & 63u);
       if (lab == kEpsilon) {

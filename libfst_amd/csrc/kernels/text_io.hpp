@@ -138,4 +138,27 @@ __global__ void __launch_bounds__(64) text_write_kernel(BatchOutDev s, uint32_t 
   }
 }
 
+// The streamed text batch (c_api.cpp), strings the pull tier handed on: once the later tiers
+// have written their paths to the arena's fixed slots, one wavefront per string (grid-stride)
+// emits them as the pull tiers' chase epilogue does (emit_text_paths with one job, held by
+// lane 0).  Strings whose `first` status is OK (emitted already) or EMPTY (final) are
+// skipped, and so is every string the later tiers left without a path.
+__global__ void __launch_bounds__(64) text_fixup_kernel(BatchOutDev s, TextOutDev tx,
+                                                        const int32_t* first, uint32_t num) {
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t i = blockIdx.x; i < num; i += gridDim.x) {
+    const int32_t f = first[i];
+    if (f == kPathOk || f == kPathEmpty || s.status[i] != kPathOk) continue;
+    const uint64_t o = s.path_off[i];
+    const uint32_t L = s.path_len[i];
+    // (the later tiers reserve the string's fixed slot, reserve_path; anything else would be
+    // an engine bug and is never read or written through)
+    if (o != s.slots[i] || L != (uint32_t)(s.slots[i + 1] - o) || o + L > s.arc_cap) {
+      if (lane == 0) s.status[i] = kPathInternal;
+      continue;
+    }
+    emit_text_paths(s, tx, 1u, i, o, L, s.final_w[i], lane, num);
+  }
+}
+
 }  // namespace fstamd

@@ -142,6 +142,8 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_u64),
                                        C.c_void_p]),
     "fst_batch_result_to_text": (C.c_int, [C.POINTER(FstBatchResult), C.POINTER(FstTextResult)]),
+    "fst_debug_text_compact": (_u64, [_u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
 }
 
 _lib = None
@@ -522,6 +524,21 @@ def batch_result_to_text(r: BatchResult) -> TextResult:
     if rc != FST_OK:
         raise RuntimeError(f"fst_batch_result_to_text failed: {rc}")
     return _take_text(res)
+
+
+def debug_text_compact(slots, nbytes, status, total_weight, text):
+    """The streamed text route's host compaction (fst_debug_text_compact) on copies of the
+    arrays: (offsets, status, total_weight, text, total bytes).  Runs without a GPU."""
+    offsets = np.array(slots, dtype=np.uint64)
+    nbytes = np.ascontiguousarray(nbytes, dtype=np.uint32)
+    status = np.array(status, dtype=np.int32)
+    total_weight = np.array(total_weight, dtype=np.float64)
+    text = np.array(text, dtype=np.uint8)
+    assert len(offsets) == len(status) + 1 == len(nbytes) + 1 == len(total_weight) + 1
+    total = lib().fst_debug_text_compact(len(status), offsets.ctypes.data, nbytes.ctypes.data,
+                                         status.ctypes.data, total_weight.ctypes.data,
+                                         text.ctypes.data)
+    return offsets, status, total_weight, text, int(total)
 
 
 def coalescer_state(device: int = 0):
