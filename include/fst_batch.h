@@ -93,6 +93,51 @@ FstError fst_compose_frozen_shortest_path_batch(FstHandle b, const uint32_t* lab
                                                 FstBatchResult* out);
 void fst_batch_result_free(FstBatchResult* r);
 
+/* Batch of general lhs FSTs: word lattices, confusion networks, n-best unions -- anything
+ * fst_compose_frozen_shortest_path takes as `a`, many at once.
+ *
+ * N lhs FSTs as one concatenated CSR (host memory).  lhs i owns the states
+ * [state_offsets[i], state_offsets[i+1]) of the per-state arrays; state ids inside
+ * an lhs (start, nextstates) are local to it.  Arcs of a state are in insertion
+ * order (MutableFst order: it decides ties, compose.zig:95-194). */
+typedef struct {
+    uint32_t num_fsts;
+    const uint64_t* state_offsets;  /* [num_fsts + 1] */
+    const uint32_t* start;          /* [num_fsts], FST_NO_STATE: no start */
+    const double*   final_weights;  /* [total_states], +inf: not final */
+    const uint64_t* arc_offsets;    /* [total_states + 1] */
+    const uint32_t* ilabels;        /* [total_arcs] */
+    const uint32_t* olabels;
+    const double*   weights;
+    const uint32_t* nextstates;     /* local to the arc's lhs */
+} FstLhsBatch;
+
+/* Per item the result is, bit for bit (labels, arc weights times(w_lhs, w_rhs), final
+ * times(fw1, fw2)),
+ *   FST_SEM_LAZY : what fst_compose_frozen_shortest_path(a_i, b, n) returns,
+ *   FST_SEM_EAGER: what fst_shortest_path(fst_compose_frozen(a_i, b), n) returns,
+ * as a status and a 1-best chain in the FstBatchResult (fst_batch_result_free,
+ * fst_batch_result_to_text work on it unchanged).  Statuses as for the chain entries: no
+ * start in the lhs (an lhs of zero states has none) or the rhs, or n == 0: EMPTY (checked
+ * before n, compose-shortest-path.zig:30-33); other n != 1: ERROR_N; a back-pointer cycle:
+ * CYCLE; a NaN weight in the item (or the rhs): UNSUPPORTED.  OVERFLOW / OUTPUT_FULL are
+ * retried internally.
+ * Checked on the host before any device work, each FST_INVALID_ARG with *out zeroed: null
+ * pointers, decreasing state_offsets or arc_offsets, arc_offsets[0] != 0, a start or
+ * nextstate at or beyond the item's state count, an item of 2^30 or more states or 2^32 or
+ * more arcs, unknown flags, an invalid rhs handle.  num_fsts == 0 gives an empty OK result.
+ * FST_BATCH_DEVICES shards the items as for the label entries (balanced by arcs + 1 per
+ * item); the result is in input order and byte-identical to a one-shard run. */
+FstError fst_compose_frozen_shortest_path_lhs_batch(FstHandle b, const FstLhsBatch* lhs,
+                                                    uint32_t n, const FstBatchOptions* opts,
+                                                    FstBatchResult* out);
+/* Same, from handles: each a[i] is snapshotted under its lock as the single call does
+ * (c-api.zig:754); an invalid handle is FST_INVALID_ARG for the call. */
+FstError fst_compose_frozen_shortest_path_handles_batch(FstHandle b, const FstMutableHandle* a,
+                                                        uint32_t num, uint32_t n,
+                                                        const FstBatchOptions* opts,
+                                                        FstBatchResult* out);
+
 /* Device-resident batch: every pointer is device memory on opts->device; the call is
  * asynchronous on `stream` (a hipStream_t, or NULL for the null stream).  Paths are
  * appended to the arc arena; *arc_cursor (device) is reset by the call.  `work`, if
@@ -231,7 +276,10 @@ typedef struct {
     uint32_t launches;          /* kernel launches in the call */
     uint32_t engine;            /* 0 = eager-layered, 1 = lazy replay, 2 = eager-general,
                                    3 = lazy rounds, 4 = lazy layered (+ rounds for the rest),
-                                   5 = lazy dense replay, 6 = shortest-path heap replay */
+                                   5 = lazy dense replay, 6 = shortest-path heap replay,
+                                   7 = lazy pull tier,
+                                   8 = lhs batch, lazy (hashed replay, one wave per lhs),
+                                   9 = lhs batch, eager (general BFS tiers, 1-best in kernel) */
     uint32_t grid;              /* workgroups of the dominant kernel */
 } FstLaunchStats;
 FstError fst_last_launch_stats(FstLaunchStats* out);

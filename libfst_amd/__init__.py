@@ -9,4 +9,6 @@ from .fst import (  # noqa: F401
     FST_PATH_OUTPUT_FULL, FST_PATH_OVERFLOW, FST_PATH_UNSUPPORTED, FST_SEM_EAGER, FST_SEM_LAZY,
     BatchResult, Fst, FstTextResult, MutableFst, TextResult, batch_result_to_text, compose_frozen,
     compose_frozen_shortest_path, coalescer_state, compose_frozen_shortest_path_batch,
-    last_launch_stats, lib, normalize_text_batch, pipeline_batch, shortest_path)
+    last_launch_stats, lib, normalize_text_batch, pipeline_batch, shortest_path,
+    FstLhsBatch, LhsBatch, compose_frozen_shortest_path_lhs_batch,
+    compose_frozen_shortest_path_handles_batch)

@@ -2650,6 +2650,269 @@ void fst_batch_result_free(FstBatchResult* r) {
   std::memset(r, 0, sizeof(*r));
 }
 
+// ---- Batch of general lhs (lattices, confusion networks, n-best unions) ----------------
+
+namespace {
+// The argument checks of the lhs batch entry, on the host alone.
+bool lhs_batch_valid(const FstLhsBatch* L) {
+  if (!L) return false;
+  const uint32_t num = L->num_fsts;
+  if (num == 0) return true;
+  if (!L->state_offsets || !L->start || !L->arc_offsets) return false;
+  // (the sizes first, from the state offsets alone: nothing below reads 2^30 states)
+  for (uint32_t i = 0; i < num; ++i) {
+    if (L->state_offsets[i + 1] < L->state_offsets[i]) return false;
+    if (L->state_offsets[i + 1] - L->state_offsets[i] >= (1ull << 30)) return false;
+  }
+  if (L->arc_offsets[0] != 0) return false;
+  const uint64_t s_end = L->state_offsets[num];
+  if (s_end && !L->final_weights) return false;
+  for (uint64_t s = 0; s < s_end; ++s)
+    if (L->arc_offsets[s + 1] < L->arc_offsets[s]) return false;
+  if (L->arc_offsets[s_end] && (!L->ilabels || !L->olabels || !L->weights || !L->nextstates))
+    return false;
+  for (uint32_t i = 0; i < num; ++i) {
+    const uint64_t s0 = L->state_offsets[i], s1 = L->state_offsets[i + 1];
+    const uint64_t ns = s1 - s0, a0 = L->arc_offsets[s0], a1 = L->arc_offsets[s1];
+    // bfs_key holds s1 in 30 bits; the item's arc offsets are u32 on the device
+    if (ns >= (1ull << 30) || a1 - a0 >= (1ull << 32)) return false;
+    if (L->start[i] != FST_NO_STATE && L->start[i] >= ns) return false;
+    for (uint64_t a = a0; a < a1; ++a)
+      if (L->nextstates[a] >= ns) return false;
+  }
+  return true;
+}
+
+// One shard (items [i0, i1) of the caller's batch) on the shard's engine: the items staged
+// into one pinned block -- descriptors, per-state arc offsets local to the item, finals, the
+// four arc arrays, the two eager item lists -- and uploaded with one DMA; then the engine
+// (DeviceEngine::run_lhs_batch), its arena grown on OUTPUT_FULL as run_chain_batch_dev does.
+FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n, int semantics) {
+  const int dev = S.E->dev();
+  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  DeviceFst* D = b.device(dev);
+  if (!D) return FST_OOM;
+  const hipStream_t stream = S.E.stream();
+  const uint32_t i0 = S.s0, num = S.s1 - S.s0;
+  const uint64_t sb = L.state_offsets[i0], ns = L.state_offsets[S.s1] - sb;
+  const uint64_t ab = L.arc_offsets[sb], na = L.arc_offsets[L.state_offsets[S.s1]] - ab;
+  auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
+  const uint64_t o_desc = 0, o_soff = al(num * 32ull), o_fin = o_soff + al((ns + num) * 4),
+                 o_w = o_fin + al(ns * 8), o_il = o_w + al(na * 8), o_ol = o_il + al(na * 4),
+                 o_nx = o_ol + al(na * 4), o_la = o_nx + al(na * 4), o_lb = o_la + al(num * 4ull),
+                 end = o_lb + al(num * 4ull);
+  DevBuf blk(end);
+  PinnedVec<uint8_t> hin(end);
+  if (!blk.p) return FST_OOM;
+  // every return drains the stream before `blk` and `hin` go back to their pools: the
+  // upload or a kernel (the engine can fail after launching some) may still be using them
+  struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+  } drain{stream};
+  LhsDesc* desc = (LhsDesc*)(hin.data() + o_desc);
+  uint32_t* soff = (uint32_t*)(hin.data() + o_soff);
+  uint32_t* la = (uint32_t*)(hin.data() + o_la);
+  uint32_t* lb = (uint32_t*)(hin.data() + o_lb);
+  if (ns) std::memcpy(hin.data() + o_fin, L.final_weights + sb, ns * 8);
+  if (na) {
+    std::memcpy(hin.data() + o_w, L.weights + ab, na * 8);
+    std::memcpy(hin.data() + o_il, L.ilabels + ab, na * 4);
+    std::memcpy(hin.data() + o_ol, L.olabels + ab, na * 4);
+    std::memcpy(hin.data() + o_nx, L.nextstates + ab, na * 4);
+  }
+  uint32_t n_a = 0, n_b = 0, max_outdeg = 0;
+  const auto neg = [](double x) { return x < 0.0 || (x == 0.0 && std::signbit(x)); };
+  for (uint32_t i = 0; i < num; ++i) {
+    const uint64_t s0 = L.state_offsets[i0 + i], s1 = L.state_offsets[i0 + i + 1];
+    const uint64_t a0 = L.arc_offsets[s0], a1 = L.arc_offsets[s1];
+    LhsDesc& d = desc[i];
+    d.state_base = s0 - sb;
+    d.arc_base = a0 - ab;
+    d.num_states = (uint32_t)(s1 - s0);
+    d.start = d.num_states ? L.start[i0 + i] : kNoState;
+    d.num_arcs = (uint32_t)(a1 - a0);
+    uint32_t fl = 0;
+    if (D->nan) fl |= kLhsNaN;
+    if (!D->nonneg) fl |= kLhsReplay;
+    uint32_t* so = soff + (s0 - sb) + i;
+    for (uint64_t s = s0; s <= s1; ++s) so[s - s0] = (uint32_t)(L.arc_offsets[s] - a0);
+    for (uint64_t s = s0; s < s1; ++s) {
+      max_outdeg = std::max(max_outdeg, so[s - s0 + 1] - so[s - s0]);
+      const double f = L.final_weights[s];
+      if (std::isnan(f)) fl |= kLhsNaN;
+      if (neg(f)) fl |= kLhsReplay;
+    }
+    for (uint64_t a = a0; a < a1; ++a) {
+      const double w = L.weights[a];
+      if (std::isnan(w)) fl |= kLhsNaN;
+      if (neg(w) || std::isinf(w)) fl |= kLhsReplay;
+      if (L.olabels[a] == kEpsilon) fl |= kLhsEpsOut;
+    }
+    d.flags = fl;
+    if (fl & kLhsReplay) lb[n_b++] = i;
+    else la[n_a++] = i;
+  }
+  if (max_outdeg >= (1u << 30)) return FST_OOM;  // the lazy per-pop table is 2 * deg + 2 entries
+  if (hipMemcpyAsync(blk.p, hin.data(), end, hipMemcpyHostToDevice, stream) != hipSuccess)
+    return FST_OOM;
+  uint8_t* p = (uint8_t*)blk.p;
+  ChainInput in{};
+  in.lhs_desc = (const LhsDesc*)(p + o_desc);
+  in.num_strings = num;
+  GraphInput g{};
+  g.state_off = (const uint32_t*)(p + o_soff);
+  g.final_w = (const double*)(p + o_fin);
+  g.arc_w = (const double*)(p + o_w);
+  g.arc_il = (const uint32_t*)(p + o_il);
+  g.arc_ol = (const uint32_t*)(p + o_ol);
+  g.arc_next = (const uint32_t*)(p + o_nx);
+  g.start = kNoState;
+  g.max_outdeg = max_outdeg;
+  if (t_prof) t_prof->lap(0);
+  uint64_t arc_cap = std::max<uint64_t>(4 * na + 16, 1024);
+  bool fixed_growth = false;
+  if (const char* e = std::getenv("FSTAMD_ARENA_ARCS"))
+    if (*e) {
+      arc_cap = std::max<uint64_t>(std::strtoull(e, nullptr, 10), 1);
+      fixed_growth = true;
+    }
+  constexpr int kAttempts = 6;
+  PinnedVec<int32_t> status(num);
+  for (int attempt = 0; attempt < kAttempts; ++attempt) {
+    auto out = std::make_unique<DevOut>(num, arc_cap);
+    if (!out->ok()) return FST_OOM;
+    LaunchStats st;
+    LhsRoute route;
+    hipError_t err = S.E->run_lhs_batch(*D, in, g, n, semantics, (const uint32_t*)(p + o_la), n_a,
+                                        (const uint32_t*)(p + o_lb), n_b, out->v, stream, &st,
+                                        &route);
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);
+    if (t_prof) {
+      t_prof->lap(2);
+      ++t_prof->runs;
+    }
+    if (err != hipSuccess) {
+      std::fprintf(stderr, "[libfst_amd] lhs batch engine failed: %s\n", hipGetErrorString(err));
+      return FST_OOM;
+    }
+    t_last_stats = st;
+    if (hipMemcpyAsync(status.data(), out->v.status, num * 4ull, hipMemcpyDeviceToHost, stream) !=
+            hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess)
+      return FST_OOM;
+    bool full = false;
+    for (uint32_t i = 0; i < num; ++i) full |= status[i] == kPathOutputFull;
+    if (!full || attempt + 1 == kAttempts) {
+      S.keep = std::move(out);
+      return FST_OK;
+    }
+    // every engine reserves a path on the cursor before it checks the capacity, so the cursor
+    // ends at the arcs the whole batch needs: one rerun suffices
+    unsigned long long need = 0;
+    if (hipMemcpyAsync(&need, out->v.cursor, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess)
+      return FST_OOM;
+    arc_cap = fixed_growth ? arc_cap * 4 : std::max<uint64_t>(arc_cap * 2, need + 1024);
+  }
+  return FST_OOM;  // unreachable: the last attempt returns above
+}
+
+FstError lhs_batch_impl(FstHandle b_handle, const FstLhsBatch* lhs, uint32_t n,
+                        const FstBatchOptions* opts, FstBatchResult* out) {
+  std::shared_ptr<FrozenFst> b = g_fst.get(b_handle);
+  if (!b) return FST_INVALID_ARG;
+  const uint32_t num = lhs->num_fsts;
+  if (num == 0) {
+    if (!alloc_result(out, 0, 0)) {
+      fst_batch_result_free(out);
+      return FST_OOM;
+    }
+    out->path_offsets[0] = 0;
+    return FST_OK;
+  }
+  if (!gpu_available()) return FST_INVALID_ARG;
+  const int semantics = opts ? (int)opts->semantics : FST_SEM_LAZY;
+  if (semantics != FST_SEM_LAZY && semantics != FST_SEM_EAGER) return FST_INVALID_ARG;
+  std::vector<int> devices;
+  uint32_t nsh = 1;
+  if (FstError e = batch_devices(opts, &devices, &nsh); e != FST_OK) return e;
+  HostProf prof;
+  t_prof = &prof;
+  struct ProfScope {
+    ~ProfScope() { t_prof = nullptr; }
+  } prof_scope;
+  std::vector<double> cost(nsh > 1 ? num : 0);
+  for (size_t i = 0; i < cost.size(); ++i)
+    cost[i] = (double)(lhs->arc_offsets[lhs->state_offsets[i + 1]] -
+                       lhs->arc_offsets[lhs->state_offsets[i]]) + 1.0;
+  const FstError e = run_sharded(
+      devices, nsh, num, cost,
+      [&](Shard& S) { return run_lhs_shard(S, *b, *lhs, n, semantics); }, out);
+  if (e != FST_OK) {
+    fst_batch_result_free(out);
+    return e;
+  }
+  prof.lap(5);
+  prof.print("fst_compose_frozen_shortest_path_lhs_batch");
+  return FST_OK;
+}
+}  // namespace
+
+FstError fst_compose_frozen_shortest_path_lhs_batch(FstHandle b_handle, const FstLhsBatch* lhs,
+                                                    uint32_t n, const FstBatchOptions* opts,
+                                                    FstBatchResult* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!lhs_batch_valid(lhs)) return FST_INVALID_ARG;
+  if (opts && (opts->flags & ~FST_BATCH_DEVICES)) return FST_INVALID_ARG;
+  return lhs_batch_impl(b_handle, lhs, n, opts, out);
+}
+
+FstError fst_compose_frozen_shortest_path_handles_batch(FstHandle b_handle,
+                                                        const FstMutableHandle* a, uint32_t num,
+                                                        uint32_t n, const FstBatchOptions* opts,
+                                                        FstBatchResult* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (num && !a) return FST_INVALID_ARG;
+  if (opts && (opts->flags & ~FST_BATCH_DEVICES)) return FST_INVALID_ARG;
+  // each lhs flattened to CSR under its own lock (the single call's snapshot, c-api.zig:754)
+  std::vector<uint64_t> state_offsets(num + 1, 0), arc_offsets(1, 0);
+  std::vector<uint32_t> start(num), il, ol, nx;
+  std::vector<double> fin, w;
+  for (uint32_t i = 0; i < num; ++i) {
+    auto g = g_mut.lock_shared(a[i]);
+    const MutableFst* m = g_mut.get_locked(a[i]);
+    if (!m) return FST_INVALID_ARG;
+    const uint32_t ns = (uint32_t)m->num_states();
+    start[i] = m->start();
+    state_offsets[i + 1] = state_offsets[i] + ns;
+    for (uint32_t s = 0; s < ns; ++s) {
+      fin.push_back(m->final_weight(s));
+      for (const Arc& x : m->arcs(s)) {
+        il.push_back(x.ilabel);
+        ol.push_back(x.olabel);
+        w.push_back(x.weight);
+        nx.push_back(x.nextstate);
+      }
+      arc_offsets.push_back(il.size());
+    }
+  }
+  FstLhsBatch L{};
+  L.num_fsts = num;
+  L.state_offsets = state_offsets.data();
+  L.start = start.data();
+  L.final_weights = fin.data();
+  L.arc_offsets = arc_offsets.data();
+  L.ilabels = il.data();
+  L.olabels = ol.data();
+  L.weights = w.data();
+  L.nextstates = nx.data();
+  if (!lhs_batch_valid(&L)) return FST_INVALID_ARG;
+  return lhs_batch_impl(b_handle, &L, n, opts, out);
+}
+
 FstError fst_device_project_output(const FstDeviceBatch* o, uint32_t num_strings,
                                    uint32_t* d_next_labels, uint64_t* d_next_offsets,
                                    int32_t* d_proj_status, uint32_t* max_len, void* stream) {

@@ -1456,14 +1456,17 @@ hipError_t DeviceEngine::launch_lazy_hashed(const DeviceFst& rhs, const ChainInp
                                             uint32_t n, const BatchOutDev& out,
                                             hipStream_t stream, uint64_t want_nodes,
                                             const uint32_t* items, uint32_t num_items,
-                                            unsigned int* ctr, uint32_t* grid_out) {
+                                            unsigned int* ctr, uint32_t* grid_out,
+                                            const GraphInput* lhs_batch) {
   GraphInput none{};
   const bool debug = std::getenv("FSTAMD_LAZY_DEBUG") != nullptr;
   LazyWs ws{};
   ws.ncap = next_pow2(want_nodes);
   ws.hcap = ws.ncap * 2;
   ws.qcap = ws.ncap * 4;
-  ws.gcap = 64;
+  // a batch of general lhs: the per-pop table holds the largest out-degree of the batch
+  // (prepare_graph: deg entries, then one per output-epsilon arc), as run_graph sizes it
+  ws.gcap = lhs_batch ? next_pow2(std::max<uint64_t>(64, 2ull * lhs_batch->max_outdeg + 2)) : 64;
   const uint64_t per_wave = (uint64_t)ws.hcap * sizeof(uint4) +
                             (uint64_t)ws.ncap * (8 + 8 + 16 + 8) +
                             (uint64_t)ws.qcap * (8 + 4) + (uint64_t)ws.gcap * sizeof(uint4);
@@ -1475,6 +1478,7 @@ hipError_t DeviceEngine::launch_lazy_hashed(const DeviceFst& rhs, const ChainInp
   const uint64_t budget = 20ull << 30;
   while (grid > 1 && (uint64_t)grid * per_wave > budget) grid /= 2;
   grid = std::max<uint32_t>(grid, 1);
+  if (lhs_batch) grid = std::min<uint32_t>(grid, grid_cap("FSTAMD_GRAPH_GRID"));
   ws.hslot = (uint4*)scratch(kLzHash, (size_t)grid * ws.hcap * sizeof(uint4));
   ws.nkey = (unsigned long long*)scratch(kLzNkey, (size_t)grid * ws.ncap * 8);
   ws.ndist = (double*)scratch(kLzNdist, (size_t)grid * ws.ncap * 8);
@@ -1499,9 +1503,14 @@ hipError_t DeviceEngine::launch_lazy_hashed(const DeviceFst& rhs, const ChainInp
   ws.wd_ticks = watchdog_ticks();
   ws.dbg = debug ? (uint32_t*)scratch(kDebug, (size_t)grid * 8 * 4) : nullptr;
   if (ws.dbg) HIP_TRY(hipMemsetAsync(ws.dbg, 0, (size_t)grid * 8 * 4, stream));
-  lazy_wave_kernel<false><<<grid, 64, 0, stream>>>(rhs.view, in, none, n, ctr, items,
-                                                   num_items, ws, out);
-  HIP_TRY(hipGetLastError());
+  if (lhs_batch) {
+    HIP_TRY(launch_lhs_lazy(rhs.view, in, *lhs_batch, n, ctr, items, num_items, ws, out, grid,
+                            stream));
+  } else {
+    lazy_wave_kernel<false><<<grid, 64, 0, stream>>>(rhs.view, in, none, n, ctr, items,
+                                                     num_items, ws, out);
+    HIP_TRY(hipGetLastError());
+  }
   if (debug) dump_debug(ws.dbg, grid, stream);
   *grid_out = grid;
   return hipSuccess;
@@ -2674,6 +2683,163 @@ hipError_t DeviceEngine::run_graph(const DeviceFst& rhs, const GraphInput& in, u
     HIP_TRY(hipEventRecord(ev1_, stream));
     HIP_TRY(finish_stats(ev0_, ev1_, stats));
   }
+  return hipSuccess;
+}
+
+// ---- batch of general lhs (lhs_batch.hip holds the kernel instances) -------------------
+
+// The eager ladder of run_bfs_chain over a device list of batch items: the LDS sizes, tier 0
+// with one wave per item, then the 256-thread tiers x8; what a tier reports OVERFLOW moves to
+// the next through collect_list_kernel.  The heap replay starts at tier 0 (its heap is in HBM).
+hipError_t DeviceEngine::run_lhs_eager(const DeviceFst& rhs, const ChainInput& in,
+                                       const GraphInput& lhs, uint32_t n, const uint32_t* items,
+                                       uint32_t count, bool replay, const BatchOutDev& out,
+                                       hipStream_t stream, LhsRoute* route, uint32_t* grid_out) {
+  if (count == 0) return hipSuccess;
+  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);  // [8..11], as run_bfs_chain
+  uint32_t* list = (uint32_t*)scratch(kBfsList, (size_t)in.num_strings * 4);
+  uint32_t* list2 = (uint32_t*)scratch(kBfsList2, (size_t)in.num_strings * 4);
+  if (!ctr || !list || !list2) return hipErrorOutOfMemory;
+  uint32_t* cnt = ctr + 8;
+  HIP_TRY(hipMemsetAsync(cnt, 0, 32, stream));
+  HIP_TRY(hipMemcpyAsync(cnt, &count, 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(list, items, (size_t)count * 4, hipMemcpyDeviceToDevice, stream));
+  const char* te = std::getenv("FSTAMD_BFS_TINY");
+  const bool tiny = !replay && !(te && std::strcmp(te, "0") == 0);
+  const uint32_t cap = grid_cap("FSTAMD_GRAPH_GRID");
+  for (int tier = tiny ? -2 : 0; count > 0; ++tier) {
+    const TinyCaps tc = tiny_caps(tier == -2 ? 1 : 2);
+    const BfsCaps c = tier < 0 ? BfsCaps{tc.n, tc.a, tc.h, tc.l, 0} : bfs_caps(tier);
+    const uint64_t fit = tier < 0 ? ~0ull : std::max<uint64_t>(1, kBfsBudget / c.stride);
+    if (kBfsBudget < c.stride) break;  // beyond the budget: those items stay OVERFLOW
+    const int kind = tier == -2 ? kLhsTierTiny128
+                     : tier == -1 ? kLhsTierTiny256
+                     : tier == 0 ? kLhsTierWave
+                                 : kLhsTierWG;
+    const uint64_t per_cu = tier < 0 ? (uint64_t)lhs_eager_per_cu(kind)
+                            : tier == 0 ? 4 * FSTAMD_BFS_WAVES64
+                                        : 1;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(
+        {(uint64_t)count, (uint64_t)num_cus_ * per_cu, fit, (uint64_t)cap});
+    BfsWs ws{};
+    ws.slab = tier < 0 ? nullptr : (uint8_t*)scratch(kBfsSlab, (size_t)grid * c.stride);
+    ws.hdr = (uint32_t*)scratch(kBfsHdr, (size_t)grid * 8 * 4);
+    if ((tier >= 0 && !ws.slab) || !ws.hdr) return hipErrorOutOfMemory;
+    ws.stride = c.stride;
+    ws.ncap = c.ncap;
+    ws.acap = c.acap;
+    ws.hcap = c.hcap;
+    ws.lcap = c.lcap;
+    ws.wd_ticks = watchdog_ticks();
+    ws.lattice_only = 0;
+    ws.lazy = 0;
+    ws.prof = nullptr;
+    if (replay) {  // heap + settled flags per workgroup (kernels/eager_bfs.hpp)
+      ws.replay =
+          (uint8_t*)scratch(kBfsHeap, (size_t)grid * ((size_t)(c.acap + 1) * 16 + c.ncap));
+      if (!ws.replay) return hipErrorOutOfMemory;
+    }
+    HIP_TRY(hipMemsetAsync(cnt + 1, 0, 8, stream));  // item counter + next list count
+    HIP_TRY(launch_lhs_eager(kind, rhs.view, in, lhs, n, cnt + 1, list, cnt, ws, out, grid,
+                             stream));
+    route->t[std::min(tier + 2, 3)] += count;
+    route->tiers_run += 1;
+    if (grid_out) *grid_out = std::max(*grid_out, grid);
+    collect_list_kernel<<<(count + 255) / 256, 256, 0, stream>>>(list, cnt, out.status,
+                                                                 kPathOverflow, list2, cnt + 2);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&count, cnt + 2, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(cnt, cnt + 2, 4, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    std::swap(list, list2);
+  }
+  return hipSuccess;
+}
+
+hipError_t DeviceEngine::run_lhs_batch(const DeviceFst& rhs, const ChainInput& in,
+                                       const GraphInput& lhs, uint32_t n, int semantics,
+                                       const uint32_t* items_nonneg, uint32_t num_nonneg,
+                                       const uint32_t* items_replay, uint32_t num_replay,
+                                       const BatchOutDev& out, hipStream_t stream,
+                                       LaunchStats* stats, LhsRoute* route) {
+  HIP_TRY(hipSetDevice(dev_));
+  if (semantics != 0 && semantics != 1) return hipErrorInvalidValue;
+  const uint32_t num = in.num_strings;
+  unsigned int* counter = (unsigned int*)scratch(kCounter, kCounterBytes);
+  if (!counter) return hipErrorOutOfMemory;
+  HIP_TRY(hipMemsetAsync(counter, 0, 64, stream));
+  HIP_TRY(hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), stream));
+  if (num == 0) return hipSuccess;
+  // every item starts as INTERNAL: an item no kernel finished can never read as a result
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out.status, kPathInternal, num, stream));
+  LhsRoute r;
+  uint32_t grid = 0;
+  if (stats) {
+    stats->engine = semantics == 0 ? 8 : 9;  // (7 is the lazy pull tier)
+    HIP_TRY(hipEventRecord(ev0_, stream));
+  }
+  if (semantics == 1) {
+    r.replay = num_replay;
+    HIP_TRY(run_lhs_eager(rhs, in, lhs, n, items_nonneg, num_nonneg, false, out, stream, &r,
+                          &grid));
+    HIP_TRY(run_lhs_eager(rhs, in, lhs, n, items_replay, num_replay, true, out, stream, &r,
+                          &grid));
+  } else {
+    // table tiers of 1024 tuples x16 up to the single call's 2^26, each over the list of the
+    // items the previous one reported OVERFLOW ([6] item counter, [7] / [9] list counts)
+    uint32_t* cur = (uint32_t*)scratch(kItems, (size_t)num * 4);
+    uint32_t* nxt = (uint32_t*)scratch(kItems2, (size_t)num * 4);
+    if (!cur || !nxt) return hipErrorOutOfMemory;
+    unsigned int* ic = counter + 6;
+    unsigned int* cur_cnt = counter + 7;
+    unsigned int* nxt_cnt = counter + 9;
+    uint32_t todo = num;
+    const uint32_t* list = nullptr;  // the first tier takes every item
+    int t = 0;
+    for (uint64_t want = 1024; want <= (1ull << 26) && todo > 0; want *= 16, ++t) {
+      HIP_TRY(hipMemsetAsync(ic, 0, 4, stream));
+      uint32_t g = 0;
+      if (launch_lazy_hashed(rhs, in, n, out, stream, want, list, todo, ic, &g, &lhs) !=
+          hipSuccess)
+        break;  // beyond its budget: those items stay OVERFLOW
+      r.t[t] = todo;
+      r.tiers_run += 1;
+      grid = std::max(grid, g);
+      HIP_TRY(hipMemsetAsync(nxt_cnt, 0, 4, stream));
+      if (list) {
+        collect_list_kernel<<<(todo + 255) / 256, 256, 0, stream>>>(
+            list, cur_cnt, out.status, kPathOverflow, nxt, nxt_cnt);
+      } else {
+        collect_status2_kernel<<<(num + 255) / 256, 256, 0, stream>>>(
+            out.status, num, kPathOverflow, kPathOverflow, nxt, nxt_cnt);
+      }
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(&todo, nxt_cnt, 4, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      std::swap(cur, nxt);
+      std::swap(cur_cnt, nxt_cnt);
+      list = cur;
+    }
+  }
+  if (stats) {
+    stats->grid = grid;
+    stats->launches = 2 * r.tiers_run;  // each tier: its kernel and the hand-over list
+    HIP_TRY(hipEventRecord(ev1_, stream));
+    HIP_TRY(finish_stats(ev0_, ev1_, stats));
+  }
+  if (std::getenv("FSTAMD_ROUTE_LOG")) {
+    if (semantics == 1)
+      std::fprintf(stderr,
+                   "[libfst_amd route] lhs batch: eager items %u | tiny128 %u tiny256 %u tier0 %u "
+                   "tier1+ %u | replay %u\n",
+                   num, r.t[0], r.t[1], r.t[2], r.t[3], r.replay);
+    else
+      std::fprintf(stderr,
+                   "[libfst_amd route] lhs batch: lazy items %u | t1k %u t16k %u t256k %u t4m %u "
+                   "t64m %u | replay 0\n",
+                   num, r.t[0], r.t[1], r.t[2], r.t[3], r.t[4]);
+  }
+  if (route) *route = r;
   return hipSuccess;
 }
 

@@ -247,14 +247,39 @@ struct ChainInput {
   // 4-B labels, or -- the streamed text batch alone (launch_pull_part with text = true: the
   // pull tiers' text instances, text_pull.hip) -- the strings as bytes, label = byte + 1.
   // One place for both, so the struct (a kernel argument) is the same for every kernel.
+  // A batch of general lhs (run_lhs_batch: the kLhsBatch instances, lhs_batch.hip) has no
+  // labels either: the place holds the items' descriptors.
   union {
     const uint32_t* labels;
     const uint8_t* text;
+    const struct LhsDesc* lhs_desc;
   };
   const uint64_t* offsets;
   uint32_t num_strings;
   uint32_t max_len;
 };
+// The lhs kind of the two general kernels (eager_bfs_kernel, lazy_wave_kernel): chain strings,
+// one general lhs (the single-call ABI), or a batch of general lhs.  false / true name the
+// first two as before.
+enum LhsKind : int { kLhsChain = 0, kLhsGraph = 1, kLhsBatch = 2 };
+// One lhs of a batch (fst_compose_frozen_shortest_path_lhs_batch), 32 B.  The batch is one
+// concatenated CSR on the device (a GraphInput of whole-batch arrays): item i's per-state
+// arc offsets (u32, local to the item, num_states + 1 of them) start at state_off[state_base
+// + i], its finals at final_w[state_base], its arcs at arc_*[arc_base]; start and nextstates
+// are local to the item.
+struct LhsDesc {
+  uint64_t state_base;
+  uint64_t arc_base;
+  uint32_t num_states;
+  uint32_t start;
+  uint32_t num_arcs;
+  uint32_t flags;   // kLhs* below
+};
+static_assert(sizeof(LhsDesc) == 32, "two 16-B loads per item");
+constexpr uint32_t kLhsReplay = 1u;  // eager: a weight that is negative, -0.0 or an arc of +inf:
+                                     // the exact heap replay (sp_replay), not the fixpoint
+constexpr uint32_t kLhsNaN = 2u;     // a NaN weight (in the item or the rhs): UNSUPPORTED
+constexpr uint32_t kLhsEpsOut = 4u;  // some arc has output epsilon
 struct GraphInput {       // CSR of a MutableFst lhs, arcs in insertion order
   const uint32_t* state_off;   // [ns + 1]
   const uint32_t* arc_il;
@@ -348,6 +373,35 @@ hipError_t launch_lazy_pull(const DeviceFst& rhs, const ChainInput& in, uint32_t
                             unsigned int* next_item, const EagerLaunch& lp,
                             const BatchOutDev& out, uint32_t grid, hipStream_t stream);
 
+// ---- batch of general lhs (lhs_batch.hip: the kLhsBatch instances of eager_bfs_kernel and
+// lazy_wave_kernel) ----
+struct BfsWs;
+struct LazyWs;
+// The eager instances: tables in LDS for 128 / 256 tuples, then HBM slabs with one wavefront
+// or one kLhsWG-thread workgroup per item.
+enum LhsTier : int { kLhsTierWave = 0, kLhsTierTiny128 = 1, kLhsTierTiny256 = 2, kLhsTierWG = 3 };
+constexpr int kLhsWG = 256;
+// Resident workgroups per CU of an eager instance.
+int lhs_eager_per_cu(int tier);
+hipError_t launch_lhs_eager(int tier, const RhsView& rhs, const ChainInput& in,
+                            const GraphInput& lhs, uint32_t n_best, unsigned int* next_item,
+                            const uint32_t* items, const uint32_t* num_items_dev,
+                            const BfsWs& ws, const BatchOutDev& out, uint32_t grid,
+                            hipStream_t stream);
+hipError_t launch_lhs_lazy(const RhsView& rhs, const ChainInput& in, const GraphInput& lhs,
+                           uint32_t n_best, unsigned int* next_item, const uint32_t* items,
+                           uint32_t num_items, const LazyWs& ws, const BatchOutDev& out,
+                           uint32_t grid, hipStream_t stream);
+// What a batch of general lhs took which way (FSTAMD_ROUTE_LOG, tests): items that entered
+// each tier.  Eager: t[0..3] = tiny128, tiny256, tier 0, tiers 1+ (summed); replay = items on
+// the heap-replay route (they appear in t[2..3] too).  Lazy: t[k] = items that entered the
+// table tier of 1024 << 4k tuples.
+struct LhsRoute {
+  uint32_t t[8] = {};
+  uint32_t replay = 0;
+  uint32_t tiers_run = 0;  // kernel launches of the tier ladders
+};
+
 // Per-device engine state: persistent workspaces (grown on demand), its own non-blocking
 // HIP stream and events.  A device has a small pool of engines (FSTAMD_ENGINES, default
 // 4): concurrent C-ABI calls each lease one, so they run side by side on separate streams
@@ -425,6 +479,19 @@ class DeviceEngine {
   static void trim_idle(int dev, const DeviceEngine* except = nullptr);
   hipError_t run_graph(const DeviceFst& rhs, const GraphInput& in, uint32_t n, int semantics,
                        const BatchOutDev& out, hipStream_t stream, LaunchStats* stats);
+  // A batch of general lhs (fst_compose_frozen_shortest_path_lhs_batch): `lhs` holds the
+  // whole batch's concatenated CSR (start / num_states unused, max_outdeg = the batch's),
+  // in.lhs_desc the items' descriptors, in.num_strings their number.  Lazy (semantics 0):
+  // the hashed replay, one wave per item, table tiers 1024 tuples x16 up to 2^26.  Eager (1):
+  // the general BFS engine's tier ladder with the 1-best in the kernel; items_nonneg /
+  // items_replay (device lists, with their host counts) split the items by
+  // LhsDesc::flags & kLhsReplay.  Items no tier holds end OVERFLOW.  Synchronises on `stream`
+  // between tiers.
+  hipError_t run_lhs_batch(const DeviceFst& rhs, const ChainInput& in, const GraphInput& lhs,
+                           uint32_t n, int semantics, const uint32_t* items_nonneg,
+                           uint32_t num_nonneg, const uint32_t* items_replay,
+                           uint32_t num_replay, const BatchOutDev& out, hipStream_t stream,
+                           LaunchStats* stats, LhsRoute* route);
   // fst_compose_frozen: the whole lattice of one general lhs (kernels/eager_bfs.hpp), on
   // `stream` (synchronised: the lattice is downloaded).
   hipError_t compose_lattice(const DeviceFst& rhs, const GraphInput& lhs, HostLattice* lat,
@@ -524,7 +591,12 @@ class DeviceEngine {
   hipError_t launch_lazy_hashed(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
                                 const BatchOutDev& out, hipStream_t stream, uint64_t want_nodes,
                                 const uint32_t* items, uint32_t num_items, unsigned int* ctr,
-                                uint32_t* grid_out);
+                                uint32_t* grid_out, const GraphInput* lhs_batch = nullptr);
+  // run_lhs_batch's eager ladder over one item list (replay: the heap-replay route).
+  hipError_t run_lhs_eager(const DeviceFst& rhs, const ChainInput& in, const GraphInput& lhs,
+                           uint32_t n, const uint32_t* items, uint32_t count, bool replay,
+                           const BatchOutDev& out, hipStream_t stream, LhsRoute* route,
+                           uint32_t* grid_out);
   hipError_t run_lazy_tiny(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
                            const BatchOutDev& out, hipStream_t stream, int tier,
                            const uint32_t* items, uint32_t num_items, unsigned int* ctr,

@@ -60,6 +60,33 @@ __device__ __forceinline__ unsigned long long reserve_path(const BatchOutDev& ou
   return out.slots ? out.slots[si] : atomicAdd(out.cursor, (unsigned long long)P);
 }
 
+// Item si of a batch of general lhs as the GraphInput the single-lhs code takes: the batch's
+// arrays moved by the item's bases.  Every descriptor word goes through readfirstlane, so the
+// pointers and counts are wave-uniform by construction (SGPRs) whatever register si came in:
+// the code downstream branches on them.  All lanes of the wave call it with
+// the same si.
+__device__ __forceinline__ GraphInput lhs_item(const GraphInput& all, const LhsDesc* desc,
+                                               uint32_t si, uint32_t& flags) {
+  const uint4* p = reinterpret_cast<const uint4*>(desc + si);
+  const uint4 a = p[0], b = p[1];
+  const auto sgpr = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+  const uint64_t sb = ((uint64_t)sgpr(a.y) << 32) | sgpr(a.x);
+  const uint64_t ab = ((uint64_t)sgpr(a.w) << 32) | sgpr(a.z);
+  const uint64_t so = sb + sgpr(si);  // one extra offset word per earlier item
+  GraphInput g = all;
+  g.state_off = all.state_off + so;
+  g.final_w = all.final_w + sb;
+  g.arc_il = all.arc_il + ab;
+  g.arc_ol = all.arc_ol + ab;
+  g.arc_w = all.arc_w + ab;
+  g.arc_next = all.arc_next + ab;
+  g.num_states = sgpr(b.x);
+  g.start = sgpr(b.y);
+  flags = sgpr(b.w);
+  g.eps_out = (flags & kLhsEpsOut) ? 1u : 0u;
+  return g;
+}
+
 // Streamed host batches (BatchOutDev::host_ol): after a batched chase, the wave copies the
 // finished paths' olabels and weights from their arena slots to the host-mapped result,
 // one string at a time so every store writes whole lines (the chase's own stores are one

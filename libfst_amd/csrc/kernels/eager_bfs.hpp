@@ -128,19 +128,21 @@ __device__ __forceinline__ T ld_agent(const T* p) {
 
 // The lhs of one item: a linear chain acceptor (batch API, compileString semantics:
 // label k on arc k -> k+1, weight One, final(L) = One) or a general MutableFst (CSR).
-template <bool kGraph>
+// kGraph: the LhsKind (device_engine.hpp); a batch item (kLhsBatch) is a general lhs whose
+// GraphInput the kernel forms per item (lhs_item).
+template <int kGraph>
 struct BfsLhs {
   const uint32_t* labels;
   uint32_t L;
   GraphInput g;
-  __device__ uint32_t start() const { return kGraph ? g.start : 0u; }
+  __device__ uint32_t start() const { return kGraph != kLhsChain ? g.start : 0u; }
   __device__ uint32_t deg(uint32_t s1) const {
-    if constexpr (kGraph) return g.state_off[s1 + 1] - g.state_off[s1];
+    if constexpr (kGraph != kLhsChain) return g.state_off[s1 + 1] - g.state_off[s1];
     return s1 < L ? 1u : 0u;
   }
   __device__ void arc(uint32_t s1, uint32_t i, uint32_t& il, uint32_t& ol, double& w,
                       uint32_t& nx) const {
-    if constexpr (kGraph) {
+    if constexpr (kGraph != kLhsChain) {
       const uint32_t a = g.state_off[s1] + i;
       il = g.arc_il[a];
       ol = g.arc_ol[a];
@@ -153,14 +155,14 @@ struct BfsLhs {
     }
   }
   __device__ double final_w(uint32_t s1) const {
-    if constexpr (kGraph) return g.final_w[s1];
+    if constexpr (kGraph != kLhsChain) return g.final_w[s1];
     return s1 == L ? w_one() : w_zero();
   }
 };
 
 // The candidates of tuple (s1, s2, f) in compose.zig's order (phases :95-121, :124-134,
 // :136-157, :160-194); emit(il, ol, w, target key).
-template <bool kGraph, class Emit>
+template <int kGraph, class Emit>
 __device__ __forceinline__ void bfs_expand(const RhsView& rhs, const BfsLhs<kGraph>& lhs,
                                            uint32_t s1, uint32_t s2, uint32_t f, Emit&& emit) {
   const uint32_t deg = lhs.deg(s1);
@@ -170,7 +172,7 @@ __device__ __forceinline__ void bfs_expand(const RhsView& rhs, const BfsLhs<kGra
     lhs.arc(s1, i, il, ol, w, nx);
     if (ol == kEpsilon) continue;
     uint32_t lo, cnt;
-    span_summary<kGraph>(rhs, s2, ol, lo, cnt);
+    span_summary<kGraph != kLhsChain>(rhs, s2, ol, lo, cnt);
     for (uint32_t a = lo; a < lo + cnt; ++a) {
       const ArcRec r = rhs.rec[a];
       emit(il, r.olabel, w_times(w, r.weight), bfs_key(nx, r.next, 0));
@@ -187,7 +189,7 @@ __device__ __forceinline__ void bfs_expand(const RhsView& rhs, const BfsLhs<kGra
     }
   }
   uint32_t elo, ecnt;
-  span_summary<kGraph>(rhs, s2, kEpsilon, elo, ecnt);
+  span_summary<kGraph != kLhsChain>(rhs, s2, kEpsilon, elo, ecnt);
   const uint32_t ehi = elo + ecnt;
   if (f != 2) {  // phase 3: rhs epsilon input alone
     const uint32_t nf = f == 0 ? 1u : f;
@@ -965,12 +967,15 @@ __host__ __device__ constexpr int tiny_waves(int k) { return k == 1 ? 3 : 2; }  
 // (A/B on config 4: with the ~3 KB rhs copied into LDS as well a string took 143 / 288 us
 // instead of 178 / 338 us, but 6 workgroups fit per CU instead of 8: no faster overall)
 
-template <int WG, bool kGraph, int kTiny = 0>
+template <int WG, int kGraph, int kTiny = 0>
 __global__ void __launch_bounds__(WG, WG == 64 ? (kTiny ? tiny_waves(kTiny) : FSTAMD_BFS_WAVES64) : 1)
 eager_bfs_kernel(RhsView rhs, ChainInput in, GraphInput graph, uint32_t n_best,
                  unsigned int* next_item, const uint32_t* items, const uint32_t* num_items_dev,
                  uint32_t num_items_host, BfsWs ws, BatchOutDev out) {
-  static_assert(kTiny == 0 || (!kGraph && WG == 64), "the tiny tiers are the chain batch's");
+  // (a batch of general lhs reads its lhs arrays from global memory -- they are L2-resident --
+  // and keeps only the tables in LDS)
+  static_assert(kTiny == 0 || (kGraph != kLhsGraph && WG == 64),
+                "the tiny tiers are the batches'");
   __shared__ BfsShared SH;
   const uint32_t tid = threadIdx.x;
   BfsTables T;
@@ -1009,7 +1014,9 @@ eager_bfs_kernel(RhsView rhs, ChainInput in, GraphInput graph, uint32_t n_best,
     lhs.g = graph;
     lhs.labels = nullptr;
     lhs.L = 0;
-    if constexpr (!kGraph) {
+    [[maybe_unused]] uint32_t iflags = 0;
+    if constexpr (kGraph == kLhsBatch) lhs.g = lhs_item(graph, in.lhs_desc, si, iflags);
+    if constexpr (kGraph == kLhsChain) {
       const uint64_t off = in.offsets[si];
       lhs.labels = in.labels + off;
       lhs.L = (uint32_t)(in.offsets[si + 1] - off);
@@ -1028,6 +1035,12 @@ eager_bfs_kernel(RhsView rhs, ChainInput in, GraphInput graph, uint32_t n_best,
       // shortest-path.zig:21-24 on the (empty if no start) lattice
       if (tid == 0) write_status(out, si, (no_start || n_best == 0) ? kPathEmpty : kPathErrorN, 0, 0);
       continue;
+    }
+    if constexpr (kGraph == kLhsBatch) {
+      if (iflags & kLhsNaN) {  // NaN has no order in the reference's compare (uniform)
+        if (tid == 0) write_status(out, si, kPathUnsupported, 0, 0);
+        continue;
+      }
     }
     if (ws.lattice_only && no_start) {  // compose.zig:33-35: empty result
       if (tid == 0) {
@@ -1551,6 +1564,9 @@ sp_graph_kernel(BfsTables T, uint32_t n_nodes, uint32_t start, uint32_t n_best, 
                         __builtin_amdgcn_s_memrealtime() + wd_ticks, !have_dist, have_dist != nullptr);
 }
 
+// (the one kernel here that is no template: a second translation unit that wants the
+// templates alone -- lhs_batch.hip -- defines FSTAMD_BFS_TEMPLATES_ONLY)
+#ifndef FSTAMD_BFS_TEMPLATES_ONLY
 __global__ void __launch_bounds__(64)
 sp_replay_kernel(BfsTables T, uint32_t n_nodes, uint32_t start, uint32_t n_best,
                  SpHeapEnt* heap, uint64_t hcap, uint8_t* settled, BatchOutDev out,
@@ -1566,5 +1582,6 @@ sp_replay_kernel(BfsTables T, uint32_t n_nodes, uint32_t start, uint32_t n_best,
   sp_replay(T, n_nodes, T.aoff[n_nodes], start, heap, hcap, settled, out, 0u,
             __builtin_amdgcn_s_memrealtime() + wd_ticks);
 }
+#endif
 
 }  // namespace fstamd

@@ -301,9 +301,11 @@ struct LazyLds {
 // LDS sizes of the LDS replay (kernels/lazy_tiny.hpp): size t holds 64 << t tuples.
 constexpr uint32_t lz_tiny_n(int t) { return 64u << t; }
 
-template <bool kGraph>
+// kGraph: the lhs kind (LhsKind: chain strings, one general lhs, or a batch of general lhs --
+// item si is lhs si of the concatenated CSR `graph_all`, described by chain.lhs_desc[si]).
+template <int kGraph>
 __global__ void __launch_bounds__(64, FSTAMD_REPLAY_WAVES)
-lazy_wave_kernel(RhsView rhs, ChainInput chain, GraphInput graph, uint32_t n_best,
+lazy_wave_kernel(RhsView rhs, ChainInput chain, GraphInput graph_all, uint32_t n_best,
                  unsigned int* next_item, const uint32_t* items, uint32_t num_items, LazyWs ws,
                  BatchOutDev out) {
   __shared__ LazyLds S;
@@ -349,7 +351,12 @@ lazy_wave_kernel(RhsView rhs, ChainInput chain, GraphInput graph, uint32_t n_bes
 
     ChainLhs cl{nullptr, 0};
     uint32_t start1;
-    if constexpr (kGraph) {
+    // batch of general lhs: the item's own GraphInput, every field wave-uniform in SGPRs
+    [[maybe_unused]] GraphInput gitem;
+    [[maybe_unused]] uint32_t iflags = 0;
+    if constexpr (kGraph == kLhsBatch) gitem = lhs_item(graph_all, chain.lhs_desc, si, iflags);
+    const GraphInput& graph = kGraph == kLhsBatch ? gitem : graph_all;
+    if constexpr (kGraph != kLhsChain) {
       start1 = graph.start;
     } else {
       const uint64_t off = chain.offsets[si];
@@ -358,7 +365,7 @@ lazy_wave_kernel(RhsView rhs, ChainInput chain, GraphInput graph, uint32_t n_bes
       start1 = 0;
     }
     auto lhs_final = [&](uint32_t s1) -> double {
-      if constexpr (kGraph) return graph.final_w[s1];
+      if constexpr (kGraph != kLhsChain) return graph.final_w[s1];
       else return cl.final_w(s1);
     };
 
@@ -376,6 +383,17 @@ lazy_wave_kernel(RhsView rhs, ChainInput chain, GraphInput graph, uint32_t n_bes
         }
       }
       continue;
+    }
+    if constexpr (kGraph == kLhsBatch) {
+      if (iflags & kLhsNaN) {  // NaN has no order in the reference's compare
+        if (lane == 0) {
+          out.status[si] = kPathUnsupported;
+          out.path_len[si] = 0;
+          out.path_off[si] = 0;
+          out.final_w[si] = w_zero();
+        }
+        continue;
+      }
     }
 
     // init tuple, id 0 (:146-153)
@@ -496,7 +514,7 @@ lazy_wave_kernel(RhsView rhs, ChainInput chain, GraphInput graph, uint32_t n_bes
       }
 
       // ---- candidates of the 4 phases in reference order ----
-      if constexpr (kGraph) prepare_graph(rhs, graph, tbl, P);
+      if constexpr (kGraph != kLhsChain) prepare_graph(rhs, graph, tbl, P);
       else prepare_chain(rhs, cl, P);
       const uint32_t C = P.n1 + P.n2 + P.n3 + P.n4;
       relax_count += C;
@@ -517,7 +535,7 @@ lazy_wave_kernel(RhsView rhs, ChainInput chain, GraphInput graph, uint32_t n_bes
         const bool act = c < C;
         Cand x{0, 0, 0, 0.0};
         if (act) {
-          if constexpr (kGraph) x = graph_cand(rhs, graph, tbl, P, c);
+          if constexpr (kGraph != kLhsChain) x = graph_cand(rhs, graph, tbl, P, c);
           else x = chain_cand(rhs, P, c);
         }
         // lookup (getOrCreate's get)

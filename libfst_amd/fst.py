@@ -69,6 +69,13 @@ def batch_options(device=-1, semantics=FST_SEM_LAZY, devices=None, shards=0) -> 
     return FstBatchOptions(device, semantics, FST_BATCH_DEVICES, int(shards), mask)
 
 
+class FstLhsBatch(C.Structure):
+    _fields_ = [("num_fsts", C.c_uint32), ("state_offsets", C.c_void_p), ("start", C.c_void_p),
+                ("final_weights", C.c_void_p), ("arc_offsets", C.c_void_p),
+                ("ilabels", C.c_void_p), ("olabels", C.c_void_p), ("weights", C.c_void_p),
+                ("nextstates", C.c_void_p)]
+
+
 class FstDeviceBatch(C.Structure):
     _fields_ = [("status", C.c_void_p), ("path_len", C.c_void_p), ("path_offset", C.c_void_p),
                 ("final_weight", C.c_void_p), ("ilabels", C.c_void_p), ("olabels", C.c_void_p),
@@ -115,6 +122,11 @@ SIGNATURES = {
     "fst_compose_frozen_shortest_path_batch": (
         C.c_int, [_u64, _P, _P, _u32, _u32, C.POINTER(FstBatchOptions), C.POINTER(FstBatchResult)]),
     "fst_batch_result_free": (None, [C.POINTER(FstBatchResult)]),
+    "fst_compose_frozen_shortest_path_lhs_batch": (
+        C.c_int, [_u64, C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstBatchResult)]),
+    "fst_compose_frozen_shortest_path_handles_batch": (
+        C.c_int, [_u64, _P, _u32, _u32, C.POINTER(FstBatchOptions), C.POINTER(FstBatchResult)]),
     "fst_device_compose_shortest_path": (
         C.c_int, [_u64, _P, _P, _u32, _u32, _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceBatch), _P]),
@@ -375,6 +387,85 @@ def compose_frozen_shortest_path_batch(b: Fst, labels, offsets, n: int = 1,
     if rc != FST_OK:
         raise RuntimeError(f"fst_compose_frozen_shortest_path_batch failed: {rc}")
     return _take_result(res, num)
+
+
+class LhsBatch:
+    """N general lhs FSTs as one concatenated CSR (FstLhsBatch, fst_batch.h): word lattices,
+    confusion networks, n-best unions.  State ids (start, nextstates) are local to each lhs;
+    a state's arcs keep their order (it decides ties)."""
+
+    def __init__(self, state_offsets, start, final_weights, arc_offsets, ilabels, olabels,
+                 weights, nextstates):
+        self.state_offsets = np.ascontiguousarray(state_offsets, dtype=np.uint64)
+        self.start = np.ascontiguousarray(start, dtype=np.uint32)
+        self.final_weights = np.ascontiguousarray(final_weights, dtype=np.float64)
+        self.arc_offsets = np.ascontiguousarray(arc_offsets, dtype=np.uint64)
+        self.ilabels = np.ascontiguousarray(ilabels, dtype=np.uint32)
+        self.olabels = np.ascontiguousarray(olabels, dtype=np.uint32)
+        self.weights = np.ascontiguousarray(weights, dtype=np.float64)
+        self.nextstates = np.ascontiguousarray(nextstates, dtype=np.uint32)
+
+    from_arrays = classmethod(lambda cls, *a, **k: cls(*a, **k))
+
+    @classmethod
+    def from_fsts(cls, fsts) -> "LhsBatch":
+        """From a list of (start, finals, arcs): `start` a state id or None / FST_NO_STATE,
+        `finals` one weight per state (inf: not final), `arcs` per state a list of
+        (ilabel, olabel, weight, nextstate) -- MutableFst.to_lists()."""
+        state_offsets, arc_offsets, start, fin = [0], [0], [], []
+        il, ol, w, nx = [], [], [], []
+        for st, finals, arcs in fsts:
+            assert len(finals) == len(arcs)
+            start.append(FST_NO_STATE if st is None else st)
+            fin.extend(finals)
+            for state_arcs in arcs:
+                for a in state_arcs:
+                    il.append(a[0])
+                    ol.append(a[1])
+                    w.append(a[2])
+                    nx.append(a[3])
+                arc_offsets.append(len(il))
+            state_offsets.append(len(fin))
+        return cls(state_offsets, start, fin, arc_offsets, il, ol, w, nx)
+
+    def __len__(self):
+        return len(self.start)
+
+    def c_struct(self) -> FstLhsBatch:
+        return FstLhsBatch(len(self.start), self.state_offsets.ctypes.data, self.start.ctypes.data,
+                           self.final_weights.ctypes.data, self.arc_offsets.ctypes.data,
+                           self.ilabels.ctypes.data, self.olabels.ctypes.data,
+                           self.weights.ctypes.data, self.nextstates.ctypes.data)
+
+
+def compose_frozen_shortest_path_lhs_batch(b: Fst, lhs: LhsBatch, n: int = 1,
+                                           semantics: int = FST_SEM_LAZY, device: int = -1,
+                                           devices=None, shards: int = 0) -> BatchResult:
+    """Batched 1-best of many general lhs FSTs against one frozen rhs
+    (fst_compose_frozen_shortest_path_lhs_batch): per item what the single call returns
+    (lazy) or fst_shortest_path(fst_compose_frozen(a_i, b)) (eager), bit for bit."""
+    opts = batch_options(device, semantics, devices, shards)
+    res = FstBatchResult()
+    cs = lhs.c_struct()
+    rc = lib().fst_compose_frozen_shortest_path_lhs_batch(b.h, C.byref(cs), n, C.byref(opts),
+                                                          C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_compose_frozen_shortest_path_lhs_batch failed: {rc}")
+    return _take_result(res, len(lhs))
+
+
+def compose_frozen_shortest_path_handles_batch(b: Fst, fsts, n: int = 1,
+                                               semantics: int = FST_SEM_LAZY, device: int = -1,
+                                               devices=None, shards: int = 0) -> BatchResult:
+    """The same from a list of MutableFst (each snapshotted under its lock)."""
+    hs = (C.c_uint64 * max(len(fsts), 1))(*[f.h for f in fsts])
+    opts = batch_options(device, semantics, devices, shards)
+    res = FstBatchResult()
+    rc = lib().fst_compose_frozen_shortest_path_handles_batch(b.h, hs, len(fsts), n,
+                                                              C.byref(opts), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_compose_frozen_shortest_path_handles_batch failed: {rc}")
+    return _take_result(res, len(fsts))
 
 
 def pipeline_batch(stages, labels, offsets, n: int = 1, semantics: int = FST_SEM_LAZY,

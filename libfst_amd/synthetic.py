@@ -105,3 +105,59 @@ def to_mutable(spec):
         for (il, ol, w, nx) in al:
             m.add_arc(s, il, ol, w, nx)
     return m
+
+
+# ---- general lhs: what a recogniser emits instead of one string ------------------------
+# Both return (start, finals, arcs per state), the item form of LhsBatch.from_fsts.
+
+def confusion_network(rng, text, max_alts=3, skip_prob=0.1):
+    """A confusion network ("sausage") over `text`: state k -> k + 1 per position, carrying
+    the position's own byte and up to max_alts - 1 other alternatives as byte labels
+    (byte + 1 on both tapes) with weights -log p (p a random distribution over the
+    alternatives: non-dyadic), and with probability skip_prob an epsilon:epsilon skip arc.
+    The last state is final with weight One."""
+    import math
+    alphabet = LETTERS + DIGITS
+    L = len(text)
+    finals = [INF] * L + [0.0]
+    arcs = [[] for _ in range(L + 1)]
+    for k, ch in enumerate(text):
+        n_alt = int(rng.integers(1, max_alts + 1))
+        alts = [ch]
+        while len(alts) < n_alt:
+            c = alphabet[int(rng.integers(0, len(alphabet)))]
+            if c not in alts:
+                alts.append(c)
+        skip = bool(rng.random() < skip_prob)
+        p = rng.random(len(alts) + (1 if skip else 0)) + 0.05
+        p = p / p.sum()
+        # (+ 0.0: a lone alternative has p = 1 and -log 1 is -0.0, which is not One; a negative
+        # zero would also send the item down the library's negative-weight route)
+        for c, pc in zip(alts, p):
+            arcs[k].append((lab(c), lab(c), -math.log(float(pc)) + 0.0, k + 1))
+        if skip:
+            arcs[k].append((0, 0, -math.log(float(p[-1])) + 0.0, k + 1))
+    return 0, finals, arcs
+
+
+def nbest_union(rng, texts):
+    """The union of n-best hypotheses as a prefix tree: one arc per byte (byte + 1 on both
+    tapes) with a random per-arc cost, one final state per distinct hypothesis with a random
+    final cost."""
+    finals, arcs = [INF], [[]]
+    child = [{}]
+    for t in texts:
+        s = 0
+        for ch in t:
+            nx = child[s].get(ch)
+            if nx is None:
+                nx = len(finals)
+                finals.append(INF)
+                arcs.append([])
+                child.append({})
+                child[s][ch] = nx
+                arcs[s].append((lab(ch), lab(ch), float(rng.random()) * 2.0, nx))
+            s = nx
+        if finals[s] == INF:
+            finals[s] = float(rng.random())
+    return 0, finals, arcs
