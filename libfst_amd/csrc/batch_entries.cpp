@@ -1,0 +1,591 @@
+// batch_entries.cpp -- the fst_batch.h C ABI: argument checks, the choice of route (streamed,
+// pipelined, sharded), the device-side entries.  (fst_debug_coalescer_state: c_api.cpp.)
+
+#include "host_rt.hpp"
+
+using namespace fstamd;
+using namespace fstamd::host;
+
+namespace {
+
+bool flags_ok(const FstBatchOptions* opts) { return !opts || !(opts->flags & ~FST_BATCH_DEVICES); }
+
+bool offsets_monotone(const uint64_t* offsets, uint32_t num) {
+  for (uint32_t i = 0; i < num; ++i)
+    if (offsets[i + 1] < offsets[i]) return false;
+  return true;
+}
+
+bool stream_enabled() {  // FSTAMD_STREAM=0 turns the streamed routes off
+  const char* se = std::getenv("FSTAMD_STREAM");
+  return !(se && std::strcmp(se, "0") == 0);
+}
+
+// The devices and shard count of a host batch call (FstBatchOptions, fst_batch.h).
+FstError batch_devices(const FstBatchOptions* opts, std::vector<int>* devices, uint32_t* nsh) {
+  devices->clear();
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return FST_INVALID_ARG;
+  if (opts && (opts->flags & FST_BATCH_DEVICES) && opts->device_mask) {
+    for (int d = 0; d < 64; ++d)
+      if (opts->device_mask >> d & 1) {
+        if (d >= count) return FST_INVALID_ARG;
+        devices->push_back(d);
+      }
+  } else {
+    int dev = opts ? opts->device : -1;
+    if (dev < 0) dev = current_device();
+    if (dev < 0 || dev >= count) return FST_INVALID_ARG;
+    devices->push_back(dev);
+  }
+  *nsh = (uint32_t)devices->size();
+  if (opts && (opts->flags & FST_BATCH_DEVICES) && opts->num_shards)
+    *nsh = std::max<uint32_t>(opts->num_shards, 1);
+  return FST_OK;
+}
+
+// A host batch entry after its argument checks: open() needs a GPU, reads the options and
+// starts the profile (t_prof, until the entry returns); close() frees the result or prints it.
+struct BatchCall {
+  int semantics = FST_SEM_LAZY;
+  std::vector<int> devices;
+  uint32_t nsh = 1;
+  HostProf prof;
+  FstError open(const FstBatchOptions* opts) {
+    if (!gpu_available()) return FST_INVALID_ARG;
+    semantics = opts ? (int)opts->semantics : FST_SEM_LAZY;
+    if (FstError e = batch_devices(opts, &devices, &nsh); e != FST_OK) return e;
+    prof = HostProf();
+    t_prof = &prof;
+    return FST_OK;
+  }
+  template <class R>
+  FstError close(FstError e, const char* name, R* out, void (*release)(R*)) {
+    if (e != FST_OK) {
+      release(out);
+      return e;
+    }
+    prof.lap(5);
+    prof.print(name);
+    return FST_OK;
+  }
+  ~BatchCall() {
+    if (t_prof == &prof) t_prof = nullptr;
+  }
+};
+
+// run_sharded's costs: the first stage's work (later stages' inputs are not known yet)
+std::vector<double> chain_costs(const FrozenFst& b, const uint64_t* offsets, uint32_t num,
+                                uint32_t nsh) {
+  std::vector<double> cost(nsh > 1 ? num : 0);
+  for (size_t i = 0; i < cost.size(); ++i) cost[i] = b.chain_cost(offsets[i + 1] - offsets[i]);
+  return cost;
+}
+
+// The engine of a device-side entry: leased on the current device, working on the caller's
+// stream `*s`.  Empty without a GPU, a current device or an engine.
+DeviceEngine::Lease current_engine(void* stream, hipStream_t* s) {
+  DeviceEngine::Lease E;
+  const int dev = gpu_available() ? current_device() : -1;
+  if (dev >= 0) E = DeviceEngine::acquire(dev);
+  if (E) *s = E.use((hipStream_t)stream);
+  return E;
+}
+
+BatchOutDev dev_out(const FstDeviceBatch* o) {
+  return BatchOutDev{o->status,  o->path_len, o->path_offset,  o->final_weight,
+                     o->ilabels, o->olabels,  o->weights,      o->arc_capacity,
+                     (unsigned long long*)o->arc_cursor, o->work};
+}
+
+// A frozen FST from its blob (len >= sizeof(Header)), in one of the two semirings of
+// weight.zig (fst.zig:43-47); null otherwise.
+std::shared_ptr<FrozenFst> frozen_from_bytes(const uint8_t* bytes, uint64_t len) {
+  Header h;
+  std::memcpy(&h, bytes, sizeof(h));
+  if (h.weight_type != kWeightTropical && h.weight_type != kWeightLog) return nullptr;
+  return FrozenFst::from_bytes(bytes, len, h.weight_type, nullptr);
+}
+
+// The argument checks of the lhs batch entry, on the host alone.
+bool lhs_batch_valid(const FstLhsBatch* L) {
+  if (!L) return false;
+  const uint32_t num = L->num_fsts;
+  if (num == 0) return true;
+  if (!L->state_offsets || !L->start || !L->arc_offsets) return false;
+  // (the sizes first, from the state offsets alone: nothing below reads 2^30 states)
+  for (uint32_t i = 0; i < num; ++i) {
+    if (L->state_offsets[i + 1] < L->state_offsets[i]) return false;
+    if (L->state_offsets[i + 1] - L->state_offsets[i] >= (1ull << 30)) return false;
+  }
+  if (L->arc_offsets[0] != 0) return false;
+  const uint64_t s_end = L->state_offsets[num];
+  if (s_end && !L->final_weights) return false;
+  for (uint64_t s = 0; s < s_end; ++s)
+    if (L->arc_offsets[s + 1] < L->arc_offsets[s]) return false;
+  if (L->arc_offsets[s_end] && (!L->ilabels || !L->olabels || !L->weights || !L->nextstates))
+    return false;
+  for (uint32_t i = 0; i < num; ++i) {
+    const uint64_t s0 = L->state_offsets[i], s1 = L->state_offsets[i + 1];
+    const uint64_t ns = s1 - s0, a0 = L->arc_offsets[s0], a1 = L->arc_offsets[s1];
+    // bfs_key holds s1 in 30 bits; the item's arc offsets are u32 on the device
+    if (ns >= (1ull << 30) || a1 - a0 >= (1ull << 32)) return false;
+    if (L->start[i] != FST_NO_STATE && L->start[i] >= ns) return false;
+    for (uint64_t a = a0; a < a1; ++a)
+      if (L->nextstates[a] >= ns) return false;
+  }
+  return true;
+}
+
+FstError lhs_batch_impl(FstHandle b_handle, const FstLhsBatch* lhs, uint32_t n,
+                        const FstBatchOptions* opts, FstBatchResult* out) {
+  std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
+  if (!b) return FST_INVALID_ARG;
+  const uint32_t num = lhs->num_fsts;
+  if (num == 0) {
+    if (!alloc_result(out, 0, 0)) {
+      fst_batch_result_free(out);
+      return FST_OOM;
+    }
+    out->path_offsets[0] = 0;
+    return FST_OK;
+  }
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  if (call.semantics != FST_SEM_LAZY && call.semantics != FST_SEM_EAGER) return FST_INVALID_ARG;
+  std::vector<double> cost(call.nsh > 1 ? num : 0);
+  for (size_t i = 0; i < cost.size(); ++i)
+    cost[i] = (double)(lhs->arc_offsets[lhs->state_offsets[i + 1]] -
+                       lhs->arc_offsets[lhs->state_offsets[i]]) + 1.0;
+  const FstError e = run_sharded(
+      call.devices, call.nsh, num, cost,
+      [&](Shard& S) { return run_lhs_shard(S, *b, *lhs, n, call.semantics); }, out);
+  return call.close(e, "fst_compose_frozen_shortest_path_lhs_batch", out, fst_batch_result_free);
+}
+
+}  // namespace
+
+extern "C" {
+
+FstError fst_compose_frozen_shortest_path_batch(FstHandle b_handle, const uint32_t* labels,
+                                                const uint64_t* offsets, uint32_t num_strings,
+                                                uint32_t n, const FstBatchOptions* opts,
+                                                FstBatchResult* out) {
+  if (!out || !offsets || (!labels && num_strings && offsets[num_strings] != offsets[0]))
+    return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!offsets_monotone(offsets, num_strings) || !flags_ok(opts)) return FST_INVALID_ARG;
+  std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
+  if (!b) return FST_INVALID_ARG;
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  const int semantics = call.semantics;
+  // an rhs without input epsilons and a pull tier first: the streamed batch, on one device
+  // or sharded over several
+  if (num_strings > 0 && stream_enabled()) {
+    StreamIo io;
+    io.labels = labels;
+    io.out = out;
+    const int e =
+        run_streamed(call.devices, call.nsh, *b, io, offsets, num_strings, n, semantics);
+    if (e != kStreamNotApplicable)
+      return call.close((FstError)e, "fst_compose_frozen_shortest_path_batch (streamed)", out,
+                        fst_batch_result_free);
+  }
+  // one device and a large batch on an rhs without input epsilons: pipelined sub-shards
+  // (FSTAMD_PIPELINE=0 keeps the one-shard path; FSTAMD_PIPELINE=k forces k sub-shards)
+  const char* pe = std::getenv("FSTAMD_PIPELINE");
+  const int want = pe && *pe ? std::atoi(pe) : -1;
+  uint32_t parts =
+      want > 0 ? (uint32_t)want : (uint32_t)std::min<uint64_t>(8, num_strings / (1u << 17));
+  parts = std::min<uint32_t>(parts, std::max<uint32_t>(num_strings, 1));
+  const bool single = call.devices.size() == 1 && call.nsh == 1;
+  if (single && want != 0 && parts >= 2) {
+    // (before hipSetDevice: every path out of this block gives the caller its device back)
+    DeviceRestore_ restore;
+    const int dev = call.devices[0];
+    DeviceFst* D = nullptr;
+    if (hipSetDevice(dev) == hipSuccess) D = b->device(dev);
+    if (D && !D->has_eps)
+      return call.close(
+          run_pipelined(dev, *b, labels, offsets, num_strings, n, semantics, parts, out),
+          "fst_compose_frozen_shortest_path_batch (pipelined)", out, fst_batch_result_free);
+  }
+  const FstError e = run_sharded(
+      call.devices, call.nsh, num_strings, chain_costs(*b, offsets, num_strings, call.nsh),
+      [&](Shard& S) {
+        HostPaths h;
+        return run_chain_batch_host(S.E, *b, labels, offsets + S.s0, S.s1 - S.s0, n, semantics,
+                                    &h, &S.keep);
+      },
+      out);
+  return call.close(e, "fst_compose_frozen_shortest_path_batch", out, fst_batch_result_free);
+}
+
+void fst_batch_result_free(FstBatchResult* r) {
+  if (!r) return;
+  pin_release(r->status);
+  pin_release(r->path_offsets);
+  pin_release(r->ilabels);
+  pin_release(r->olabels);
+  pin_release(r->weights);
+  pin_release(r->final_weights);
+  std::memset(r, 0, sizeof(*r));
+}
+
+// ---- Batch of general lhs (lattices, confusion networks, n-best unions) ----------------
+
+FstError fst_compose_frozen_shortest_path_lhs_batch(FstHandle b_handle, const FstLhsBatch* lhs,
+                                                    uint32_t n, const FstBatchOptions* opts,
+                                                    FstBatchResult* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!lhs_batch_valid(lhs) || !flags_ok(opts)) return FST_INVALID_ARG;
+  return lhs_batch_impl(b_handle, lhs, n, opts, out);
+}
+
+FstError fst_compose_frozen_shortest_path_handles_batch(FstHandle b_handle,
+                                                        const FstMutableHandle* a, uint32_t num,
+                                                        uint32_t n, const FstBatchOptions* opts,
+                                                        FstBatchResult* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if ((num && !a) || !flags_ok(opts)) return FST_INVALID_ARG;
+  // each lhs flattened to CSR under its own lock (the single call's snapshot, c-api.zig:754)
+  std::vector<uint64_t> state_offsets(num + 1, 0), arc_offsets(1, 0);
+  std::vector<uint32_t> start(num), il, ol, nx;
+  std::vector<double> fin, w;
+  for (uint32_t i = 0; i < num; ++i) {
+    const MutableRead r = mutable_read(a[i]);
+    const MutableFst* m = r.fst;
+    if (!m) return FST_INVALID_ARG;
+    const uint32_t ns = (uint32_t)m->num_states();
+    start[i] = m->start();
+    state_offsets[i + 1] = state_offsets[i] + ns;
+    for (uint32_t s = 0; s < ns; ++s) {
+      fin.push_back(m->final_weight(s));
+      for (const Arc& x : m->arcs(s)) {
+        il.push_back(x.ilabel);
+        ol.push_back(x.olabel);
+        w.push_back(x.weight);
+        nx.push_back(x.nextstate);
+      }
+      arc_offsets.push_back(il.size());
+    }
+  }
+  const FstLhsBatch L{num,       state_offsets.data(), start.data(), fin.data(), arc_offsets.data(),
+                      il.data(), ol.data(),            w.data(),     nx.data()};
+  if (!lhs_batch_valid(&L)) return FST_INVALID_ARG;
+  return lhs_batch_impl(b_handle, &L, n, opts, out);
+}
+
+FstError fst_device_project_output(const FstDeviceBatch* o, uint32_t num_strings,
+                                   uint32_t* d_next_labels, uint64_t* d_next_offsets,
+                                   int32_t* d_proj_status, uint32_t* max_len, void* stream) {
+  if (!o || !d_next_offsets || !d_proj_status || (num_strings && !d_next_labels))
+    return FST_INVALID_ARG;
+  uint32_t ml = 0;
+  hipStream_t s = nullptr;
+  DeviceEngine::Lease E = current_engine(stream, &s);
+  if (!E) return FST_INVALID_ARG;
+  if (E->project_output(dev_out(o), num_strings, d_next_labels, d_next_offsets, d_proj_status,
+                        &ml, s) != hipSuccess)
+    return FST_OOM;
+  if (max_len) *max_len = ml;
+  return FST_OK;
+}
+
+FstError fst_pipeline_batch(const FstHandle* stages, uint32_t num_stages, const uint32_t* labels,
+                            const uint64_t* offsets, uint32_t num_strings, uint32_t n,
+                            const FstBatchOptions* opts, FstBatchResult* out) {
+  if (!out || !stages || num_stages == 0 || !offsets ||
+      (!labels && num_strings && offsets[num_strings] != offsets[0]))
+    return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!offsets_monotone(offsets, num_strings) || !flags_ok(opts)) return FST_INVALID_ARG;
+  Stages fs(num_stages);
+  for (uint32_t k = 0; k < num_stages; ++k)
+    if (!(fs[k] = frozen_get(stages[k]))) return FST_INVALID_ARG;
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  const FstError e = run_sharded(
+      call.devices, call.nsh, num_strings, chain_costs(*fs[0], offsets, num_strings, call.nsh),
+      [&](Shard& S) {
+        return run_pipeline_shard(S, fs, labels, offsets + S.s0, n, call.semantics);
+      },
+      out);
+  return call.close(e, "fst_pipeline_batch", out, fst_batch_result_free);
+}
+
+// ---- Text entries (fst_batch.h) ---------------------------------------------------------
+
+FstError fst_normalize_text_batch(const FstHandle* stages, uint32_t num_stages,
+                                  const uint8_t* text, const uint64_t* offsets,
+                                  uint32_t num_strings, const FstBatchOptions* opts,
+                                  FstTextResult* out) {
+  if (!out || !stages || num_stages == 0 || !offsets ||
+      (!text && num_strings && offsets[num_strings] != offsets[0]))
+    return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!offsets_monotone(offsets, num_strings) || !flags_ok(opts)) return FST_INVALID_ARG;
+  Stages fs(num_stages);
+  for (uint32_t k = 0; k < num_stages; ++k)
+    if (!(fs[k] = frozen_get(stages[k]))) return FST_INVALID_ARG;
+  if (num_strings == 0) {  // nothing to run: the empty result
+    if (!alloc_text_result(out, 0, 0)) {
+      fst_text_result_free(out);
+      return FST_OOM;
+    }
+    out->text_offsets[0] = 0;
+    return FST_OK;
+  }
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  const int semantics = call.semantics;
+  // one stage on an rhs without input epsilons and a pull tier first: the streamed text
+  // batch, on one device or sharded over several
+  if (num_stages == 1 && stream_enabled()) {
+    StreamIo io;
+    io.text = text;
+    io.tout = out;
+    const int e =
+        run_streamed(call.devices, call.nsh, *fs[0], io, offsets, num_strings, 1, semantics);
+    if (e != kStreamNotApplicable)
+      return call.close((FstError)e, "fst_normalize_text_batch (streamed)", out,
+                        fst_text_result_free);
+  }
+  const FstError e = run_sharded(
+      call.devices, call.nsh, num_strings, chain_costs(*fs[0], offsets, num_strings, call.nsh),
+      [&](Shard& S) { return run_text_shard(S, fs, text, offsets + S.s0, semantics); }, out);
+  return call.close(e, "fst_normalize_text_batch", out, fst_text_result_free);
+}
+
+void fst_text_result_free(FstTextResult* r) {
+  if (!r) return;
+  pin_release(r->status);
+  pin_release(r->text_offsets);
+  pin_release(r->text);
+  pin_release(r->total_weight);
+  std::memset(r, 0, sizeof(*r));
+}
+
+FstError fst_device_compile_text(const uint8_t* d_text, const uint64_t* d_offsets,
+                                 uint32_t num_strings, uint32_t* d_labels, void* stream) {
+  if (!d_offsets) return FST_INVALID_ARG;
+  hipStream_t s = nullptr;
+  DeviceEngine::Lease E = current_engine(stream, &s);
+  if (!E) return FST_INVALID_ARG;
+  return E->widen_text(d_text, d_offsets, num_strings, d_labels, s) == hipSuccess ? FST_OK
+                                                                                 : FST_OOM;
+}
+
+FstError fst_device_emit_text(const FstDeviceBatch* o, uint32_t num_strings, uint8_t* d_text,
+                              uint64_t text_capacity, uint64_t* d_text_offsets,
+                              int32_t* d_status, double* d_total_weight, uint64_t* total_bytes,
+                              void* stream) {
+  if (!o || !d_text_offsets || !d_status || !d_total_weight || (text_capacity && !d_text))
+    return FST_INVALID_ARG;
+  const BatchOutDev v = dev_out(o);
+  hipStream_t s = nullptr;
+  DeviceEngine::Lease E = current_engine(stream, &s);
+  if (!E) return FST_INVALID_ARG;
+  uint64_t tot = 0;
+  if (E->text_count(v, num_strings, nullptr, d_status, d_text_offsets, d_total_weight, &tot, s) !=
+          hipSuccess ||
+      E->text_write(v, num_strings, d_status, d_text_offsets, d_text, text_capacity, s) !=
+          hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return FST_OOM;
+  if (total_bytes) *total_bytes = tot;
+  return FST_OK;
+}
+
+FstError fst_batch_result_to_text(const FstBatchResult* in, FstTextResult* out) {
+  if (!in || !out) return FST_INVALID_ARG;
+  const uint32_t num = in->num_strings;
+  if (num && (!in->status || !in->path_offsets || !in->final_weights)) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!offsets_monotone(in->path_offsets, num)) return FST_INVALID_ARG;
+  if (num && in->path_offsets[num] != in->path_offsets[0] && (!in->olabels || !in->weights))
+    return FST_INVALID_ARG;
+  // pass 1: statuses and byte counts; pass 2: the bytes and the fold
+  std::vector<int32_t> st(num);
+  std::vector<uint64_t> cnt(num, 0);
+  uint64_t tot = 0;
+  for (uint32_t i = 0; i < num; ++i) {
+    st[i] = in->status[i];
+    if (st[i] != kPathOk) continue;
+    uint64_t c = 0;
+    for (uint64_t k = in->path_offsets[i]; k < in->path_offsets[i + 1]; ++k) {
+      if (in->olabels[k] > 256u) {
+        st[i] = kPathUnsupported;
+        break;
+      }
+      c += in->olabels[k] != kEpsilon;
+    }
+    if (st[i] == kPathOk) cnt[i] = c;
+    tot += cnt[i];
+  }
+  if (!alloc_text_result(out, num, tot)) {
+    fst_text_result_free(out);
+    return FST_OOM;
+  }
+  uint64_t w = 0;
+  for (uint32_t i = 0; i < num; ++i) {
+    out->status[i] = st[i];
+    out->text_offsets[i] = w;
+    out->total_weight[i] = w_zero();
+    if (st[i] != kPathOk) continue;
+    double d = w_one();
+    for (uint64_t k = in->path_offsets[i]; k < in->path_offsets[i + 1]; ++k) {
+      if (in->olabels[k] != kEpsilon) out->text[w++] = (uint8_t)(in->olabels[k] - 1u);
+      d = w_times(d, in->weights[k]);
+    }
+    out->total_weight[i] = w_times(d, in->final_weights[i]);
+  }
+  out->text_offsets[num] = w;
+  return FST_OK;
+}
+
+FstError fst_device_compose_shortest_path(FstHandle b_handle, const uint32_t* d_labels,
+                                          const uint64_t* d_offsets, uint32_t num_strings,
+                                          uint32_t max_len, uint32_t n,
+                                          const FstBatchOptions* opts, const FstDeviceBatch* o,
+                                          void* stream) {
+  if (!o || !d_offsets) return FST_INVALID_ARG;
+  std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
+  if (!b) return FST_INVALID_ARG;
+  if (!gpu_available()) return FST_INVALID_ARG;
+  int dev = opts && opts->device >= 0 ? opts->device : current_device();
+  if (dev < 0 || hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  DeviceFst* D = b->device(dev);
+  if (!D) return FST_OOM;
+  ChainInput in{d_labels, d_offsets, num_strings, max_len};
+  DeviceEngine::Lease E = DeviceEngine::acquire(dev);
+  if (!E) return FST_INVALID_ARG;
+  const hipStream_t s = E.use((hipStream_t)stream);
+  LaunchStats st;
+  const int semantics = opts ? (int)opts->semantics : FST_SEM_LAZY;
+  if (E->run_chain(*D, in, n, semantics, dev_out(o), s, &st) != hipSuccess) return FST_OOM;
+  t_last_stats = st;
+  return FST_OK;
+}
+
+FstError fst_device_prepare(FstHandle b_handle, int32_t device) {
+  std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
+  if (!b) return FST_INVALID_ARG;
+  if (!gpu_available()) return FST_INVALID_ARG;
+  const int dev = device >= 0 ? device : current_device();
+  return b->device(dev) ? FST_OK : FST_OOM;
+}
+
+FstHandle fst_device_adopt_blob(const void* d_blob, uint64_t len, int32_t device,
+                                const void* host_copy) {
+  if (!d_blob || len < sizeof(Header)) return kInvalid;
+  if (!gpu_available()) return kInvalid;
+  const int dev = device >= 0 ? device : current_device();
+  if (hipSetDevice(dev) != hipSuccess) return kInvalid;
+  std::vector<uint8_t> bytes(len);
+  if (host_copy) std::memcpy(bytes.data(), host_copy, len);
+  else if (hipMemcpy(bytes.data(), d_blob, len, hipMemcpyDeviceToHost) != hipSuccess)
+    return kInvalid;
+  auto f = frozen_from_bytes(bytes.data(), len);
+  if (!f) return kInvalid;
+  DeviceFst* D = DeviceFst::adopt(d_blob, *f, dev);
+  if (!D) return kInvalid;
+  f->adopt_device(dev, D);
+  return frozen_insert(std::move(f));
+}
+
+FstError fst_last_launch_stats(FstLaunchStats* out) {
+  if (!out) return FST_INVALID_ARG;
+  out->kernel_ms = t_last_stats.kernel_ms;
+  out->launches = t_last_stats.launches;
+  out->engine = t_last_stats.engine;
+  out->grid = t_last_stats.grid;
+  return FST_OK;
+}
+
+FstHandle fst_batch_load_bytes(const void* bytes, uint64_t len) {
+  if (!bytes || len < sizeof(Header)) return kInvalid;
+  auto f = frozen_from_bytes((const uint8_t*)bytes, len);
+  return f ? frozen_insert(std::move(f)) : kInvalid;
+}
+
+FstHandle fst_batch_load(const char* path) {
+  if (!path) return kInvalid;
+  auto f = FrozenFst::load_file(path, FrozenFst::kAnyWeightType, nullptr);
+  if (!f) return kInvalid;
+  return frozen_insert(std::move(f));
+}
+
+FstHandle fst_load_att(const char* path, uint32_t flags) {
+  if (!path || (flags & ~FST_ATT_SHIFT_BYTE_LABELS)) return kInvalid;
+  std::vector<char> data;  // att2lfst.zig:40-45 (.limited(256 MiB))
+  if (!read_file(path, 256l << 20, &data)) return kInvalid;
+  MutableFst m;
+  if (!MutableFst::read_text(data.data(), data.size(), &m)) return kInvalid;
+  if (flags & FST_ATT_SHIFT_BYTE_LABELS) m.shift_labels();
+  return frozen_insert(FrozenFst::from_mutable(m, kWeightTropical));
+}
+
+double fst_chain_cost(FstHandle b, uint64_t len) {
+  auto f = frozen_get(b);
+  return f ? f->chain_cost(len) : -1.0;
+}
+
+uint64_t fst_debug_text_compact(uint32_t num_strings, uint64_t* offsets, const uint32_t* nbytes,
+                                int32_t* status, double* total_weight, uint8_t* text) {
+  if (!offsets || (num_strings && (!nbytes || !status || !total_weight))) return 0;
+  return text_compact(num_strings, offsets, nbytes, status, total_weight, text);
+}
+
+int32_t fst_weight_type(FstHandle b) {
+  auto f = frozen_get(b);
+  return f ? (int32_t)f->weight_type() : -1;
+}
+
+// Reference bench rhs generators (bench/optimize-bench.zig:219-306).
+FstHandle fst_bench_transducer(uint32_t kind, uint32_t T, uint32_t B) {
+  return fst_bench_transducer_wt(kind, T, B, kWeightTropical);
+}
+
+FstHandle fst_bench_transducer_wt(uint32_t kind, uint32_t T, uint32_t B, uint32_t weight_type) {
+  if (weight_type != kWeightTropical && weight_type != kWeightLog) return kInvalid;
+  MutableFst m;
+  if (kind == 0) {  // buildAmbiguousChainTransducer, :250-277
+    m.add_states(T + 1);
+    m.set_start(0);
+    for (uint32_t i = 0; i <= T; ++i) m.set_final(i, w_one());
+    const uint32_t fan = std::max<uint32_t>(1, std::min<uint32_t>(B, 4));
+    for (uint32_t i = 0; i <= T; ++i) {
+      m.add_arc(i, Arc{1, 1, w_one(), i});
+      for (uint32_t b = 0; b < fan; ++b)
+        m.add_arc(i, Arc{1, ((i + b) % 255) + 1, (double)b, std::min(i + b + 1, T)});
+    }
+  } else if (kind == 1) {  // buildEpsilonDenseTransducer, :219-248
+    m.add_states(T + 1);
+    m.set_start(0);
+    for (uint32_t i = 0; i <= T; ++i) m.set_final(i, w_one());
+    for (uint32_t i = 0; i < T; ++i) {
+      m.add_arc(i, Arc{0, 0, w_one(), i + 1});
+      for (uint32_t b = 0; b < B; ++b)
+        m.add_arc(i, Arc{1, ((i + b) % 255) + 1, (double)b, std::min(i + (b % 4) + 1, T)});
+    }
+  } else if (kind == 2) {  // transducer_for_freeze, :290-306
+    if (T == 0) return kInvalid;
+    m.add_states(T);
+    m.set_start(0);
+    for (uint32_t i = 0; i < T; ++i) {
+      m.set_final(i, w_one());
+      for (uint32_t b = 0; b < B; ++b)
+        m.add_arc(i, Arc{(b % 255) + 1, ((i + b) % 255) + 1, (double)b,
+                         (uint32_t)(((uint64_t)i + b + 1) % T)});
+    }
+  } else {
+    return kInvalid;
+  }
+  return frozen_insert(FrozenFst::from_mutable(m, (uint8_t)weight_type));
+}
+
+}  // extern "C"

@@ -1,0 +1,653 @@
+// batch_sharded.cpp -- host batches through the path arena: one engine run with arena
+// growth, the shards of a call and their result sinks (labels, text), the pipelined
+// one-device batch, and the per-shard compute steps (pipeline stages, text, general lhs).
+#include <cmath>
+#include <condition_variable>
+
+#include "host_rt.hpp"
+
+namespace fstamd::host {
+namespace {
+
+// One engine run into a path arena of `arc_cap` slots, rerun with a larger arena while a
+// string is OUTPUT_FULL.  `launch` queues the engine on `stream`; `failed` names it in the
+// error message.  With `keep` the device outputs stay alive and `h` receives only the
+// statuses; without it `h` receives everything.  `fine_laps`: the chain route's profile
+// also times the arena allocation and the download on their own.
+using ArenaLaunch = std::function<hipError_t(const BatchOutDev&, LaunchStats*)>;
+FstError run_arena(hipStream_t stream, uint32_t num, uint64_t arc_cap, const char* failed,
+                   bool fine_laps, const ArenaLaunch& launch, HostPaths* h,
+                   std::unique_ptr<DevOut>* keep) {
+  // test override: the first arena size, grown x4 per attempt (so that 6 attempts can run
+  // out, tests/test_gpu_watchdog.py) instead of sized from the demand
+  bool fixed_growth = false;
+  if (const char* e = std::getenv("FSTAMD_ARENA_ARCS"))
+    if (*e) {
+      arc_cap = std::max<uint64_t>(std::strtoull(e, nullptr, 10), 1);
+      fixed_growth = true;
+    }
+  constexpr int kAttempts = 6;
+  for (int attempt = 0; attempt < kAttempts; ++attempt) {
+    if (t_prof && fine_laps) t_prof->lap(7);
+    auto out = std::make_unique<DevOut>(num, arc_cap);
+    if (!out->ok()) return FST_OOM;
+    if (t_prof && fine_laps) t_prof->lap(1);
+    LaunchStats st;
+    hipError_t err = launch(out->v, &st);
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);
+    if (t_prof) {
+      t_prof->lap(2);
+      ++t_prof->runs;
+    }
+    if (err != hipSuccess) {
+      std::fprintf(stderr, "[libfst_amd] %s: %s\n", failed, hipGetErrorString(err));
+      return FST_OOM;
+    }
+    t_last_stats = st;
+    if (keep) {
+      h->status.resize(num);
+      if (!d2h(h->status.data(), out->v.status, num * 4ull, stream) ||
+          hipStreamSynchronize(stream) != hipSuccess)
+        return FST_OOM;
+    } else if (!out->download(num, h, stream)) {
+      return FST_OOM;
+    }
+    if (t_prof && fine_laps) t_prof->lap(3);
+    bool full = false;
+    for (uint32_t i = 0; i < num; ++i) full |= h->status[i] == kPathOutputFull;
+    // The last attempt's result stands: strings still OUTPUT_FULL keep that status (the
+    // caller sees FST_PATH_OUTPUT_FULL per string), and `keep` is always set on FST_OK.
+    if (!full || attempt + 1 == kAttempts) {
+      if (keep) *keep = std::move(out);
+      return FST_OK;
+    }
+    // every engine reserves a path with atomicAdd on the cursor before it checks the
+    // capacity, so the cursor ends at the arcs the whole batch needs: one rerun suffices
+    unsigned long long need = 0;
+    if (!read_u64(&need, out->v.cursor, stream)) return FST_OOM;
+    arc_cap = fixed_growth ? arc_cap * 4 : std::max<uint64_t>(arc_cap * 2, need + 1024);
+  }
+  return FST_OOM;  // unreachable: the last attempt returns above
+}
+
+// The offsets of a batch from its first label, and its longest string.
+uint32_t rebase_offsets(const uint64_t* offsets, uint32_t num, std::vector<uint64_t>* rebased) {
+  uint32_t max_len = 0;
+  rebased->resize(num + 1);
+  for (uint32_t i = 0; i < num; ++i) {
+    (*rebased)[i] = offsets[i] - offsets[0];
+    max_len = std::max<uint32_t>(max_len, (uint32_t)(offsets[i + 1] - offsets[i]));
+  }
+  (*rebased)[num] = offsets[num] - offsets[0];
+  return max_len;
+}
+
+FstError shard_compact(Shard& S) {
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  const DevOut& o = *S.keep;
+  unsigned long long used = 0;
+  if (!read_u64(&used, o.cursor.p, stream)) return FST_OOM;
+  used = std::min<unsigned long long>(used, o.v.arc_cap);
+  S.st = std::make_unique<DevBuf>(num * 4ull);
+  S.off = std::make_unique<DevBuf>((num + 1ull) * 8);
+  S.fin = std::make_unique<DevBuf>(num * 8ull);
+  S.il = std::make_unique<DevBuf>(used * 4);
+  S.ol = std::make_unique<DevBuf>(used * 4);
+  S.w = std::make_unique<DevBuf>(used * 8);
+  if (!S.st->p || !S.off->p || !S.fin->p || !S.il->p || !S.ol->p || !S.w->p) return FST_OOM;
+  if (S.E->compact_paths(o.v, num, S.fail ? (const int32_t*)S.fail->p : nullptr,
+                         (int32_t*)S.st->p, (uint64_t*)S.off->p, (uint32_t*)S.il->p,
+                         (uint32_t*)S.ol->p, (double*)S.w->p, (double*)S.fin->p, used, &S.tot,
+                         stream) != hipSuccess)
+    return FST_OOM;
+  if (S.tot > used) return FST_OOM;  // an engine bug (the gather wrote nothing past `used`)
+  return FST_OK;
+}
+
+// D2H of a compacted shard into the (pinned) result, asynchronously on `stream`: no
+// synchronisation and no offset fix-up (the pipelined host batch does both once at the end).
+bool shard_download_async(Shard& S, FstBatchResult* out, uint64_t arc_base, hipStream_t stream) {
+  const uint32_t num = S.s1 - S.s0;
+  return d2h(out->status + S.s0, S.st->p, num * 4ull, stream) &&
+         d2h(out->final_weights + S.s0, S.fin->p, num * 8ull, stream) &&
+         d2h(out->path_offsets + S.s0, S.off->p, num * 8ull, stream) &&
+         d2h(out->ilabels + arc_base, S.il->p, S.tot * 4, stream) &&
+         d2h(out->olabels + arc_base, S.ol->p, S.tot * 4, stream) &&
+         d2h(out->weights + arc_base, S.w->p, S.tot * 8, stream);
+}
+
+// The same on the shard's stream, one synchronisation, then its path offsets moved by the
+// shard's first arc.
+FstError shard_download(Shard& S, FstBatchResult* out, uint64_t arc_base) {
+  const hipStream_t stream = S.E.stream();
+  if (!shard_download_async(S, out, arc_base, stream) || hipStreamSynchronize(stream) != hipSuccess)
+    return FST_OOM;
+  if (arc_base)
+    for (uint32_t i = S.s0; i < S.s1; ++i) out->path_offsets[i] += arc_base;
+  return FST_OK;
+}
+
+// ---- Text results (fst_normalize_text_batch) -------------------------------------------
+// The text phase of a shard, in compact_paths' place: count and scan the output bytes of the
+// last stage's paths, then write them (DeviceEngine::text_count / text_write).
+FstError shard_text(Shard& S) {
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  const DevOut& o = *S.keep;
+  S.st = std::make_unique<DevBuf>(num * 4ull);
+  S.off = std::make_unique<DevBuf>((num + 1ull) * 8);
+  S.fin = std::make_unique<DevBuf>(num * 8ull);
+  if (!S.st->p || !S.off->p || !S.fin->p) return FST_OOM;
+  if (S.E->text_count(o.v, num, S.fail ? (const int32_t*)S.fail->p : nullptr, (int32_t*)S.st->p,
+                      (uint64_t*)S.off->p, (double*)S.fin->p, &S.tot, stream) != hipSuccess)
+    return FST_OOM;
+  S.text = std::make_unique<DevBuf>(S.tot);
+  if (!S.text->p) return FST_OOM;
+  // (synchronised: the download may run on another engine's stream)
+  if (S.E->text_write(o.v, num, (const int32_t*)S.st->p, (const uint64_t*)S.off->p,
+                      (uint8_t*)S.text->p, S.tot, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return FST_OOM;
+  S.keep.reset();  // the path arena is not downloaded
+  return FST_OK;
+}
+
+FstError shard_text_download(Shard& S, FstTextResult* out, uint64_t byte_base) {
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  if (!(d2h(out->status + S.s0, S.st->p, num * 4ull, stream) &&
+        d2h(out->total_weight + S.s0, S.fin->p, num * 8ull, stream) &&
+        d2h(out->text_offsets + S.s0, S.off->p, num * 8ull, stream) &&
+        d2h(out->text + byte_base, S.text->p, S.tot, stream)) ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return FST_OOM;
+  if (byte_base)
+    for (uint32_t i = S.s0; i < S.s1; ++i) out->text_offsets[i] += byte_base;
+  return FST_OK;
+}
+
+// The stages of one shard on device inputs (labels `lab`, offsets `off`, in_total labels).
+FstError run_pipeline_stages(Shard& S, const Stages& fs, std::unique_ptr<DevBuf> lab,
+                             std::unique_ptr<DevBuf> off, uint64_t in_total, uint32_t max_len,
+                             uint32_t n, int semantics) {
+  DeviceEngine::Lease& E = S.E;
+  const int dev = S.dev;
+  const uint32_t num_strings = S.s1 - S.s0;
+  const hipStream_t stream = E.stream();
+  S.fail = std::make_unique<DevBuf>(num_strings * 4ull);  // first failing stage per string
+  if (!S.fail->p || hipMemsetAsync(S.fail->p, 0, num_strings * 4ull, stream) != hipSuccess)
+    return FST_OOM;
+  HostPaths h;
+  for (size_t k = 0; k < fs.size(); ++k) {
+    DeviceFst* D = fs[k]->device(dev);
+    if (!D) return FST_OOM;
+    ChainInput in{(const uint32_t*)lab->p, (const uint64_t*)off->p, num_strings, max_len};
+    S.keep.reset();
+    FstError e = run_chain_batch_dev(E, *D, in, in_total, n, semantics, &h, &S.keep);
+    if (e != FST_OK) return e;
+    if (!S.keep) return FST_OOM;  // run_chain_batch_dev sets it on FST_OK
+    if (k + 1 == fs.size()) break;
+    // project this stage's outputs into the next stage's inputs, on the device
+    unsigned long long used = 0;
+    if (!read_u64(&used, S.keep->v.cursor, stream)) return FST_OOM;
+    auto nlab = std::make_unique<DevBuf>((used + num_strings) * 4);
+    auto noff = std::make_unique<DevBuf>((num_strings + 1ull) * 8);
+    DevBuf pst(num_strings * 4ull);
+    if (!nlab->p || !noff->p || !pst.p) return FST_OOM;
+    if (E->project_output(S.keep->v, num_strings, (uint32_t*)nlab->p, (uint64_t*)noff->p,
+                          (int32_t*)pst.p, &max_len, stream) != hipSuccess ||
+        E->merge_status((int32_t*)S.fail->p, (const int32_t*)pst.p, num_strings, stream) !=
+            hipSuccess)
+      return FST_OOM;
+    // (synchronises: pst may go back to the pool)
+    if (!read_u64(&in_total, (uint64_t*)noff->p + num_strings, stream)) return FST_OOM;
+    lab = std::move(nlab);
+    off = std::move(noff);
+    if (t_prof) t_prof->lap(4);
+  }
+  return FST_OK;
+}
+
+}  // namespace
+
+FstError run_chain_batch_dev(DeviceEngine::Lease& E, DeviceFst& D, const ChainInput& in,
+                             uint64_t total_labels, uint32_t n, int semantics, HostPaths* h,
+                             std::unique_ptr<DevOut>* keep) {
+  const hipStream_t stream = E.stream();
+  // Arena: chains without rhs epsilons produce exactly L arcs per path; with them a path
+  // also carries the rhs epsilon arcs (a tagger's or verbalizer's multi-symbol outputs),
+  // so start at 4 arcs per label rather than run the whole batch twice on OUTPUT_FULL.
+  const uint64_t arc_cap = std::max<uint64_t>((D.has_eps ? 4 : 1) * total_labels + 16, 1024);
+  return run_arena(
+      stream, in.num_strings, arc_cap, "batch engine failed", true,
+      [&](const BatchOutDev& v, LaunchStats* st) {
+        return E->run_chain(D, in, n, semantics, v, stream, st);
+      },
+      h, keep);
+}
+
+bool alloc_result(FstBatchResult* out, uint32_t num, uint64_t tot) {
+  out->num_strings = num;
+  out->total_arcs = tot;
+  out->status = (int32_t*)pin_alloc(std::max<size_t>(num, 1) * 4);
+  out->path_offsets = (uint64_t*)pin_alloc((num + 1ull) * 8);
+  out->final_weights = (double*)pin_alloc(std::max<size_t>(num, 1) * 8);
+  out->ilabels = (uint32_t*)pin_alloc(std::max<uint64_t>(tot, 1) * 4);
+  out->olabels = (uint32_t*)pin_alloc(std::max<uint64_t>(tot, 1) * 4);
+  out->weights = (double*)pin_alloc(std::max<uint64_t>(tot, 1) * 8);
+  return out->status && out->path_offsets && out->final_weights && out->ilabels &&
+         out->olabels && out->weights;
+}
+
+bool alloc_text_result(FstTextResult* out, uint32_t num, uint64_t tot) {
+  out->num_strings = num;
+  out->total_bytes = tot;
+  out->status = (int32_t*)pin_alloc(std::max<size_t>(num, 1) * 4);
+  out->text_offsets = (uint64_t*)pin_alloc((num + 1ull) * 8);
+  out->total_weight = (double*)pin_alloc(std::max<size_t>(num, 1) * 8);
+  out->text = (uint8_t*)pin_alloc(std::max<uint64_t>(tot, 1));
+  return out->status && out->text_offsets && out->total_weight && out->text;
+}
+
+FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
+                     const std::vector<double>& cost, const ShardCompute& compute,
+                     const ShardSink& sink) {
+  // shard 0 runs on the calling thread and switches its current device: give the caller
+  // its device back on every return (later calls that use current_device() rely on it)
+  DeviceRestore_ restore;
+  nsh = std::max<uint32_t>(1, std::min<uint32_t>(nsh, std::max<uint32_t>(num, 1)));
+  std::vector<Shard> sh(nsh);
+  if (nsh == 1) {
+    sh[0].dev = devices[0];
+    sh[0].s0 = 0;
+    sh[0].s1 = num;
+  } else {
+    double total = 0;
+    for (double c : cost) total += c;
+    uint32_t i = 0;
+    double acc = 0;
+    for (uint32_t j = 0; j < nsh; ++j) {
+      sh[j].dev = devices[j % devices.size()];
+      sh[j].s0 = i;
+      const double goal = total * (j + 1) / nsh;
+      // leave at least one string for each later shard
+      while (i < num && (j + 1 == nsh || (acc + cost[i] <= goal && num - i > nsh - 1 - j))) {
+        acc += cost[i];
+        ++i;
+      }
+      if (j + 1 < nsh && i == sh[j].s0 && i < num) acc += cost[i++];  // never empty
+      sh[j].s1 = (j + 1 == nsh) ? num : i;
+    }
+  }
+  if (std::getenv("FSTAMD_SHARD_LOG"))  // tests: the shard plan
+    for (uint32_t j = 0; j < nsh; ++j) {
+      double c = 0;
+      for (uint32_t i = sh[j].s0; i < sh[j].s1 && i < cost.size(); ++i) c += cost[i];
+      std::fprintf(stderr, "[libfst_amd shard] %u dev %d strings %u..%u cost %.6g route sharded\n", j,
+                   sh[j].dev, sh[j].s0, sh[j].s1, c);
+    }
+  auto phase1 = [&](Shard& S) {
+    if (hipSetDevice(S.dev) != hipSuccess) {
+      S.err = FST_INVALID_ARG;
+      return;
+    }
+    S.E = DeviceEngine::acquire(S.dev);
+    if (!S.E) {
+      S.err = FST_INVALID_ARG;
+      return;
+    }
+    S.err = compute(S);
+    S.stats = t_last_stats;
+    if (S.err == FST_OK && !S.keep) S.err = FST_OOM;
+    if (S.err == FST_OK) S.err = sink.compact(S);
+    // no lease is held between the phases: a shard waiting for an engine never holds one
+    // (two sharded calls on one device cannot deadlock)
+    S.E = DeviceEngine::Lease();
+  };
+  auto phase2 = [&](Shard& S, uint64_t base) {
+    if (hipSetDevice(S.dev) != hipSuccess) {
+      S.err = FST_OOM;
+      return;
+    }
+    S.E = DeviceEngine::acquire(S.dev);
+    S.err = S.E ? sink.download(S, base) : FST_OOM;
+    S.E = DeviceEngine::Lease();
+  };
+  auto each = [&](const std::function<void(uint32_t)>& f) {
+    if (nsh == 1) return f(0);
+    std::vector<std::thread> th;
+    for (uint32_t j = 1; j < nsh; ++j) th.emplace_back(f, j);
+    f(0);
+    for (auto& x : th) x.join();
+  };
+  each([&](uint32_t j) { phase1(sh[j]); });
+  uint64_t tot = 0;
+  for (Shard& S : sh) {
+    if (S.err != FST_OK) return S.err;
+    tot += S.tot;
+  }
+  if (t_prof) t_prof->lap(4);
+  if (!sink.alloc(tot)) return FST_OOM;
+  std::vector<uint64_t> base(nsh, 0);
+  for (uint32_t j = 1; j < nsh; ++j) base[j] = base[j - 1] + sh[j - 1].tot;
+  each([&](uint32_t j) { phase2(sh[j], base[j]); });
+  sink.finish(tot);
+  LaunchStats agg = sh[0].stats;  // the slowest shard's kernel time, launches summed
+  for (uint32_t j = 1; j < nsh; ++j) {
+    agg.kernel_ms = std::max(agg.kernel_ms, sh[j].stats.kernel_ms);
+    agg.launches += sh[j].stats.launches;
+  }
+  t_last_stats = agg;
+  for (Shard& S : sh)
+    if (S.err != FST_OK) return S.err;
+  if (t_prof) t_prof->lap(3);
+  return FST_OK;
+}
+
+FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
+                     const std::vector<double>& cost, const ShardCompute& compute,
+                     FstBatchResult* out) {
+  const ShardSink sink{shard_compact,
+                       [=](uint64_t tot) { return alloc_result(out, num, tot); },
+                       [=](Shard& S, uint64_t base) { return shard_download(S, out, base); },
+                       [=](uint64_t tot) { out->path_offsets[num] = tot; }};
+  return run_sharded(devices, nsh, num, cost, compute, sink);
+}
+
+FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
+                     const std::vector<double>& cost, const ShardCompute& compute,
+                     FstTextResult* out) {
+  const ShardSink sink{shard_text,
+                       [=](uint64_t tot) { return alloc_text_result(out, num, tot); },
+                       [=](Shard& S, uint64_t base) { return shard_text_download(S, out, base); },
+                       [=](uint64_t tot) { out->text_offsets[num] = tot; }};
+  return run_sharded(devices, nsh, num, cost, compute, sink);
+}
+
+// One device, one large batch on an rhs without input epsilons (a path has exactly L arcs,
+// so the result is allocated before any shard finishes): the strings run as consecutive
+// sub-shards on one engine, and the download of sub-shard j (a second stream, waiting for
+// j's compaction only) runs while sub-shard j + 1 computes -- round 3's host batch ran its
+// ~1 GB D2H after all the kernels.  Results are identical to the one-shard path.
+FstError run_pipelined(int dev, FrozenFst& b, const uint32_t* labels, const uint64_t* offsets,
+                       uint32_t num, uint32_t n, int semantics, uint32_t parts,
+                       FstBatchResult* out) {
+  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  DeviceFst* D = b.device(dev);
+  if (!D) return FST_OOM;
+  DeviceEngine::Lease E = DeviceEngine::acquire(dev);
+  if (!E) return FST_INVALID_ARG;
+  const hipStream_t stream = E.stream();
+  struct OwnStream {  // a stream of the call's own and its events: drained, then destroyed
+    hipStream_t s = nullptr;
+    std::vector<hipEvent_t> ev;
+    ~OwnStream() {
+      if (s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+      }
+      for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+  } C;  // the downloads' stream and the compaction events it waits for
+  if (hipStreamCreateWithFlags(&C.s, hipStreamNonBlocking) != hipSuccess) return FST_OOM;
+  std::vector<uint64_t> rebased;
+  rebase_offsets(offsets, num, &rebased);
+  const uint64_t total = rebased[num];
+  DevBuf d_lab(total * 4), d_off((num + 1) * 8ull);
+  if (!d_lab.p || !d_off.p) return FST_OOM;
+  if (hipMemcpyAsync(d_off.p, rebased.data(), (num + 1) * 8ull, hipMemcpyHostToDevice, stream) !=
+      hipSuccess)
+    return FST_OOM;
+  std::vector<Shard> sh(parts);
+  // every return drains the engine stream before the buffers its kernels use (d_lab, d_off,
+  // the sub-shards' outputs: declared above, destroyed after this) go back to the pool
+  StreamDrain sync_engine{{stream}};
+  for (uint32_t j = 0; j < parts; ++j) {
+    sh[j].dev = dev;
+    sh[j].s0 = (uint32_t)((uint64_t)num * j / parts);
+    sh[j].s1 = (uint32_t)((uint64_t)num * (j + 1) / parts);
+  }
+  // The labels go up per sub-shard on a thread and stream of their own (a pageable source
+  // is staged through pinned memory on the copying thread), so sub-shard j + 1's upload
+  // runs while sub-shard j computes; the engine's stream waits on each upload's event.
+  struct Uploader : OwnStream {  // (the thread joined before the stream goes)
+    std::mutex mu;
+    std::condition_variable cv;
+    uint32_t ready = 0;
+    bool failed = false;
+    std::thread th;
+    ~Uploader() {
+      if (th.joinable()) th.join();
+    }
+  } U;
+  if (hipStreamCreateWithFlags(&U.s, hipStreamNonBlocking) != hipSuccess) return FST_OOM;
+  U.ev.assign(parts, nullptr);
+  for (uint32_t j = 0; j < parts; ++j)
+    if (hipEventCreateWithFlags(&U.ev[j], hipEventDisableTiming) != hipSuccess) return FST_OOM;
+  U.th = std::thread([&, dev] {
+    bool ok = hipSetDevice(dev) == hipSuccess;
+    for (uint32_t j = 0; j < parts; ++j) {
+      const uint64_t a = rebased[sh[j].s0], z = rebased[sh[j].s1];
+      ok = ok && (z == a || hipMemcpyAsync((uint32_t*)d_lab.p + a, labels + offsets[0] + a,
+                                           (z - a) * 4, hipMemcpyHostToDevice, U.s) == hipSuccess);
+      ok = ok && hipEventRecord(U.ev[j], U.s) == hipSuccess;
+      std::lock_guard<std::mutex> g(U.mu);
+      if (!ok) {
+        U.failed = true;
+        U.cv.notify_all();
+        return;
+      }
+      U.ready = j + 1;
+      U.cv.notify_all();
+    }
+  });
+  if (t_prof) t_prof->lap(0);
+  if (!alloc_result(out, num, total)) return FST_OOM;  // paths of L arcs: <= total arcs
+  // every return below first waits for the downloads in flight: on an error the caller
+  // frees the result, whose pinned pages must not be written after that
+  StreamDrain sync_copies{{C.s}};
+  uint64_t base = 0;
+  for (uint32_t j = 0; j < parts; ++j) {
+    Shard& S = sh[j];
+    {
+      std::unique_lock<std::mutex> g(U.mu);
+      U.cv.wait(g, [&] { return U.failed || U.ready > j; });
+      if (U.failed) return FST_OOM;
+    }
+    if (hipStreamWaitEvent(stream, U.ev[j], 0) != hipSuccess) return FST_OOM;
+    uint32_t ml = 0;
+    for (uint32_t i = S.s0; i < S.s1; ++i) ml = std::max<uint32_t>(ml, (uint32_t)(rebased[i + 1] - rebased[i]));
+    // the sub-shard reads the whole upload: its offsets index the one label array
+    ChainInput in{(const uint32_t*)d_lab.p, (const uint64_t*)d_off.p + S.s0, S.s1 - S.s0, ml};
+    HostPaths h;
+    if (FstError e = run_chain_batch_dev(E, *D, in, rebased[S.s1] - rebased[S.s0], n, semantics,
+                                         &h, &S.keep);
+        e != FST_OK)
+      return e;
+    S.stats = t_last_stats;
+    S.E = std::move(E);  // shard_compact runs on the lease's stream
+    const FstError ce = shard_compact(S);
+    E = std::move(S.E);
+    if (ce != FST_OK) return ce;
+    if (base + S.tot > total) return FST_OOM;  // (a path longer than its string: impossible)
+    hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return FST_OOM;
+    C.ev.push_back(ev);
+    if (hipEventRecord(ev, stream) != hipSuccess || hipStreamWaitEvent(C.s, ev, 0) != hipSuccess ||
+        !shard_download_async(S, out, base, C.s))
+      return FST_OOM;
+    S.keep.reset();  // (the path arena: compaction copied what the download needs)
+    base += S.tot;
+  }
+  if (hipStreamSynchronize(C.s) != hipSuccess) return FST_OOM;
+  if (t_prof) t_prof->lap(3);
+  uint64_t acc = 0;
+  for (uint32_t j = 0; j < parts; ++j) {
+    if (acc)
+      for (uint32_t i = sh[j].s0; i < sh[j].s1; ++i) out->path_offsets[i] += acc;
+    acc += sh[j].tot;
+  }
+  out->path_offsets[num] = base;
+  out->total_arcs = base;
+  LaunchStats agg = sh[0].stats;
+  agg.kernel_ms = 0;
+  agg.launches = 0;
+  for (const Shard& S : sh) {
+    agg.kernel_ms += S.stats.kernel_ms;
+    agg.launches += S.stats.launches;
+  }
+  t_last_stats = agg;
+  return FST_OK;
+}
+
+// One shard of a pipeline: every stage on the shard's device, each stage's 1-best output tape
+// projected into the next stage's inputs on the device; S.keep = the last stage's outputs,
+// S.fail = the first failing stage per string.
+FstError run_pipeline_shard(Shard& S, const Stages& fs, const uint32_t* labels,
+                            const uint64_t* offsets, uint32_t n, int semantics) {
+  const uint32_t num_strings = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  // stage-1 inputs
+  std::vector<uint64_t> rebased;
+  const uint32_t max_len = rebase_offsets(offsets, num_strings, &rebased);
+  const uint64_t total = rebased[num_strings];
+  auto lab = std::make_unique<DevBuf>(total * 4), off = std::make_unique<DevBuf>((num_strings + 1ull) * 8);
+  if (!lab->p || !off->p) return FST_OOM;
+  if (total && hipMemcpyAsync(lab->p, labels + offsets[0], total * 4, hipMemcpyHostToDevice,
+                              stream) != hipSuccess)
+    return FST_OOM;
+  if (hipMemcpyAsync(off->p, rebased.data(), (num_strings + 1ull) * 8, hipMemcpyHostToDevice,
+                     stream) != hipSuccess)
+    return FST_OOM;
+  if (t_prof) t_prof->lap(0);
+  return run_pipeline_stages(S, fs, std::move(lab), std::move(off), total, max_len, n, semantics);
+}
+
+// The text entry's shard: the bytes and their offsets go up as they are, the device widens
+// them to stage-1 labels (DeviceEngine::widen_text), then the same stages.
+FstError run_text_shard(Shard& S, const Stages& fs, const uint8_t* text, const uint64_t* offsets,
+                        int semantics) {
+  const uint32_t num_strings = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  std::vector<uint64_t> rebased;
+  const uint32_t max_len = rebase_offsets(offsets, num_strings, &rebased);
+  const uint64_t total = rebased[num_strings];
+  // `bytes` is read by the widen kernel only; it and `rebased` live until the first stage
+  // has synchronised the stream, and every failure drains the stream before they go
+  StreamDrain drain{{stream}};
+  DevBuf bytes(total);
+  auto lab = std::make_unique<DevBuf>(total * 4), off = std::make_unique<DevBuf>((num_strings + 1ull) * 8);
+  if (!bytes.p || !lab->p || !off->p) return FST_OOM;
+  if (total && hipMemcpyAsync(bytes.p, text + offsets[0], total, hipMemcpyHostToDevice, stream) !=
+                   hipSuccess)
+    return FST_OOM;
+  if (hipMemcpyAsync(off->p, rebased.data(), (num_strings + 1ull) * 8, hipMemcpyHostToDevice,
+                     stream) != hipSuccess)
+    return FST_OOM;
+  if (S.E->widen_text((const uint8_t*)bytes.p, (const uint64_t*)off->p, num_strings,
+                      (uint32_t*)lab->p, stream) != hipSuccess)
+    return FST_OOM;
+  if (t_prof) t_prof->lap(0);
+  const FstError e =
+      run_pipeline_stages(S, fs, std::move(lab), std::move(off), total, max_len, 1, semantics);
+  drain.done = e == FST_OK;  // (run_chain_batch_dev synchronised it)
+  return e;
+}
+
+// One shard (items [i0, i1) of the caller's batch) on the shard's engine: the items staged
+// into one pinned block -- descriptors, per-state arc offsets local to the item, finals, the
+// four arc arrays, the two eager item lists -- and uploaded with one DMA; then the engine
+// (DeviceEngine::run_lhs_batch), its arena grown on OUTPUT_FULL as run_chain_batch_dev's is.
+FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n, int semantics) {
+  const int dev = S.E->dev();
+  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  DeviceFst* D = b.device(dev);
+  if (!D) return FST_OOM;
+  const hipStream_t stream = S.E.stream();
+  const uint32_t i0 = S.s0, num = S.s1 - S.s0;
+  const uint64_t sb = L.state_offsets[i0], ns = L.state_offsets[S.s1] - sb;
+  const uint64_t ab = L.arc_offsets[sb], na = L.arc_offsets[L.state_offsets[S.s1]] - ab;
+  auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
+  const uint64_t o_desc = 0, o_soff = al(num * 32ull), o_fin = o_soff + al((ns + num) * 4),
+                 o_w = o_fin + al(ns * 8), o_il = o_w + al(na * 8), o_ol = o_il + al(na * 4),
+                 o_nx = o_ol + al(na * 4), o_la = o_nx + al(na * 4), o_lb = o_la + al(num * 4ull),
+                 end = o_lb + al(num * 4ull);
+  DevBuf blk(end);
+  PinnedVec<uint8_t> hin(end);
+  if (!blk.p) return FST_OOM;
+  // every return drains the stream before `blk` and `hin` go back to their pools: the
+  // upload or a kernel (the engine can fail after launching some) may still be using them
+  StreamDrain drain{{stream}};
+  LhsDesc* desc = (LhsDesc*)(hin.data() + o_desc);
+  uint32_t* soff = (uint32_t*)(hin.data() + o_soff);
+  uint32_t* la = (uint32_t*)(hin.data() + o_la);
+  uint32_t* lb = (uint32_t*)(hin.data() + o_lb);
+  if (ns) std::memcpy(hin.data() + o_fin, L.final_weights + sb, ns * 8);
+  if (na) {
+    std::memcpy(hin.data() + o_w, L.weights + ab, na * 8);
+    std::memcpy(hin.data() + o_il, L.ilabels + ab, na * 4);
+    std::memcpy(hin.data() + o_ol, L.olabels + ab, na * 4);
+    std::memcpy(hin.data() + o_nx, L.nextstates + ab, na * 4);
+  }
+  uint32_t n_a = 0, n_b = 0, max_outdeg = 0;
+  const auto neg = [](double x) { return x < 0.0 || (x == 0.0 && std::signbit(x)); };
+  for (uint32_t i = 0; i < num; ++i) {
+    const uint64_t s0 = L.state_offsets[i0 + i], s1 = L.state_offsets[i0 + i + 1];
+    const uint64_t a0 = L.arc_offsets[s0], a1 = L.arc_offsets[s1];
+    LhsDesc& d = desc[i];
+    d.state_base = s0 - sb;
+    d.arc_base = a0 - ab;
+    d.num_states = (uint32_t)(s1 - s0);
+    d.start = d.num_states ? L.start[i0 + i] : kNoState;
+    d.num_arcs = (uint32_t)(a1 - a0);
+    uint32_t fl = 0;
+    if (D->nan) fl |= kLhsNaN;
+    if (!D->nonneg) fl |= kLhsReplay;
+    uint32_t* so = soff + (s0 - sb) + i;
+    for (uint64_t s = s0; s <= s1; ++s) so[s - s0] = (uint32_t)(L.arc_offsets[s] - a0);
+    for (uint64_t s = s0; s < s1; ++s) {
+      max_outdeg = std::max(max_outdeg, so[s - s0 + 1] - so[s - s0]);
+      const double f = L.final_weights[s];
+      if (std::isnan(f)) fl |= kLhsNaN;
+      if (neg(f)) fl |= kLhsReplay;
+    }
+    for (uint64_t a = a0; a < a1; ++a) {
+      const double w = L.weights[a];
+      if (std::isnan(w)) fl |= kLhsNaN;
+      if (neg(w) || std::isinf(w)) fl |= kLhsReplay;
+      if (L.olabels[a] == kEpsilon) fl |= kLhsEpsOut;
+    }
+    d.flags = fl;
+    if (fl & kLhsReplay) lb[n_b++] = i;
+    else la[n_a++] = i;
+  }
+  if (max_outdeg >= (1u << 30)) return FST_OOM;  // the lazy per-pop table is 2 * deg + 2 entries
+  if (hipMemcpyAsync(blk.p, hin.data(), end, hipMemcpyHostToDevice, stream) != hipSuccess)
+    return FST_OOM;
+  uint8_t* p = (uint8_t*)blk.p;
+  ChainInput in{};
+  in.lhs_desc = (const LhsDesc*)(p + o_desc);
+  in.num_strings = num;
+  GraphInput g{};
+  g.state_off = (const uint32_t*)(p + o_soff);
+  g.final_w = (const double*)(p + o_fin);
+  g.arc_w = (const double*)(p + o_w);
+  g.arc_il = (const uint32_t*)(p + o_il);
+  g.arc_ol = (const uint32_t*)(p + o_ol);
+  g.arc_next = (const uint32_t*)(p + o_nx);
+  g.start = kNoState;
+  g.max_outdeg = max_outdeg;
+  if (t_prof) t_prof->lap(0);
+  HostPaths h;  // (the statuses)
+  return run_arena(
+      stream, num, std::max<uint64_t>(4 * na + 16, 1024), "lhs batch engine failed", false,
+      [&](const BatchOutDev& v, LaunchStats* st) {
+        LhsRoute route;
+        return S.E->run_lhs_batch(*D, in, g, n, semantics, (const uint32_t*)(p + o_la), n_a,
+                                  (const uint32_t*)(p + o_lb), n_b, v, stream, st, &route);
+      },
+      &h, &S.keep);
+}
+
+}  // namespace fstamd::host

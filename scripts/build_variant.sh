@@ -11,6 +11,7 @@ mkdir -p $vdir build_var
 HIPCC=/opt/rocm/bin/hipcc
 $HIPCC -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -ffp-contract=off $defs --offload-arch=gfx950 \
   -c eager_pull.hip -o build_var/$name.o
+objs=$(make -s print-objs)  # the release objects, with the one rebuilt here swapped in
 $HIPCC -shared -fPIC --offload-arch=gfx950 -o $vdir/$name.so \
-  build/host_fst.cpp.o build/c_api.cpp.o build/device_engine.hip.o build_var/$name.o
+  ${objs/build\/eager_pull.hip.o/build_var/$name.o}
 echo "built $vdir/$name.so ($defs)"

@@ -1,4 +1,4 @@
-"""The streamed host batch (c_api.cpp run_streamed): a batch of >= 4 M labels and >= 32 K
+"""The streamed host batch (batch_streamed.cpp run_streamed): a batch of >= 4 M labels and >= 32 K
 strings on an rhs whose first tier is a pull tier runs as parts of growing size over two
 engines, the pull tier alone per part (its statuses written twice by the kernel, its paths
 copied into the pinned result by the kernel), then the later tiers once over the strings it
@@ -186,3 +186,38 @@ def test_streamed_shards_on_one_gpu(metric, sem, shards, monkeypatch, capfd):
     edges = np.asarray([s for sp in spans for s in (sp[0], sp[1] - 1)])
     idx = np.unique(np.concatenate([edges, rng.choice(num, 40, replace=False)])).astype(np.int64)
     compare_sample(many, blob, labels, offsets, sem, idx)
+
+
+@pytest.mark.parametrize("sem", [EAGER, LAZY])
+def test_streamed_equals_sharded_more_shards_than_devices(sem, monkeypatch, capfd):
+    # 3 shards on one device through both routes of the batch entry, byte for byte: 257
+    # strings of length 0..40 (empty ones, also at shard boundaries), a tenth of them with a
+    # label the rhs has no arc for (no path: compacted out by the streamed route on the host,
+    # by the sharded route on the device)
+    rhs = F.Fst.bench_transducer(F.BENCH_AMBIGUOUS, 256, 12)
+    rng = np.random.default_rng(257)
+    seqs = []
+    for L in rng.integers(0, 41, 257):
+        q = np.ones(L, np.uint32)
+        if L and rng.random() < 0.1:
+            q[int(rng.integers(0, L))] = 3
+        seqs.append(q)
+    offsets = np.concatenate([[0], np.cumsum([len(q) for q in seqs])]).astype(np.uint64)
+    labels = np.concatenate(seqs).astype(np.uint32)
+    monkeypatch.setenv("FSTAMD_SHARD_LOG", "1")
+
+    def run():
+        capfd.readouterr()
+        r = F.compose_frozen_shortest_path_batch(rhs, labels, offsets, 1, sem, devices=[0],
+                                                 shards=3)
+        err = capfd.readouterr().err
+        plan = [ln.split() for ln in err.splitlines() if ln.startswith("[libfst_amd shard]")]
+        return r, [p[-1] for p in plan], err
+
+    streamed, routes, err = run()
+    assert routes == ["streamed"] * 3, err[-2000:]
+    monkeypatch.setenv("FSTAMD_STREAM", "0")
+    sharded, routes, err = run()
+    assert routes == ["sharded"] * 3, err[-2000:]
+    assert (streamed.status != F.FST_PATH_OK).any() and (streamed.status == F.FST_PATH_OK).any()
+    same_result(streamed, sharded)
