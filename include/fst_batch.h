@@ -189,6 +189,66 @@ FstError fst_pipeline_batch(const FstHandle* stages, uint32_t num_stages, const 
                             const uint64_t* offsets, uint32_t num_strings, uint32_t n,
                             const FstBatchOptions* opts, FstBatchResult* out);
 
+/* Pipelines on a general first stage: lattices in, labels or text out (a recogniser's
+ * confusion networks through tagger -> verbalizer without a host round trip in between).
+ * Per item, bit for bit:
+ *   - stage 1 is what fst_compose_frozen_shortest_path_lhs_batch(stages[0], lhs, n, opts)
+ *     returns for the item, statuses and path;
+ *   - each later stage takes the previous stage's 1-best output tape as a chain, exactly as
+ *     fst_pipeline_batch does between its stages (fst_device_project_output: the non-epsilon
+ *     olabels are the next input, an olabel above 256 makes the item FST_PATH_UNSUPPORTED, an
+ *     item that failed earlier reports that stage's status).
+ * fst_pipeline_lhs_batch returns the last stage's paths as an ordinary FstBatchResult
+ * (fst_batch_result_free, fst_batch_result_to_text).  fst_normalize_lhs_batch (n is 1) returns
+ * the text fst_normalize_text_batch documents below for every producer, emitted on the
+ * device: no path arena is downloaded; with num_stages == 1 it equals
+ * fst_batch_result_to_text of the lhs batch entry's result byte for byte.
+ * Checked on the host before any device work, each FST_INVALID_ARG with *out zeroed:
+ * everything fst_compose_frozen_shortest_path_lhs_batch checks (the same validator), a null
+ * `stages`, num_stages == 0, an invalid stage handle.  num_fsts == 0 gives the empty OK
+ * result.  FST_BATCH_DEVICES shards as the lhs batch entry does (arcs + 1 per item); the
+ * result is in input order and byte-identical to a one-shard run.
+ * (fst_normalize_lhs_batch is declared after FstTextResult, below.) */
+FstError fst_pipeline_lhs_batch(const FstHandle* stages, uint32_t num_stages,
+                                const FstLhsBatch* lhs, uint32_t n,
+                                const FstBatchOptions* opts, FstBatchResult* out);
+
+/* Device-resident batch of general lhs: the struct `d_lhs` is in host memory, every pointer
+ * in it is device memory on opts->device, in FstLhsBatch's layout.  The finals and the four
+ * arc arrays are used in place; a kernel derives what the host entry derives while it stages
+ * a batch (per-item descriptors, arc offsets local to the item, the weight flags, the largest
+ * out-degree) into workspaces of the library's own, O(items + states) bytes.
+ *   - Trusted extents: total_states = state_offsets[num_fsts] and total_arcs =
+ *     arc_offsets[total_states].  The host reads these two values and trusts them as the
+ *     extents of the per-state arrays (total_states entries; arc_offsets one more) and of the
+ *     arc arrays (total_arcs entries): the caller guarantees the arrays are that long.
+ *     Nothing outside those extents is read.
+ *   - The host cannot read the rest, so FST_INVALID_ARG is only: a null `out`, `d_lhs`, arc
+ *     cursor or needed array, unknown flags or semantics, an invalid handle.  What the host
+ *     entry rejects per item the kernel checks per item -- state_offsets[i] <=
+ *     state_offsets[i + 1] <= total_states, fewer than 2^30 states, arc_offsets non-decreasing
+ *     over the item's states and ending at or below total_arcs, fewer than 2^32 arcs, a start
+ *     that is FST_NO_STATE or below the item's state count, every nextstate below it -- and
+ *     an item that fails is never traversed and reports FST_PATH_UNSUPPORTED; the other items
+ *     are unaffected.  One exception: state_offsets must be non-decreasing over the whole
+ *     batch, as the host entry demands, because only then do the items own disjoint state
+ *     ranges.  If state_offsets[i] > state_offsets[i + 1] for any i, no item is traversed and
+ *     every item reports FST_PATH_UNSUPPORTED.
+ *   - Statuses in the single call's order: no start in the lhs or the rhs, or n == 0: EMPTY;
+ *     other n != 1: ERROR_N; then UNSUPPORTED (an invalid item, a NaN weight).
+ *   - Output as for fst_device_compose_shortest_path, so the result chains into
+ *     fst_device_project_output, fst_device_compose_shortest_path and fst_device_emit_text: a
+ *     device-resident lattice -> text pipeline.  The arena is the caller's: items that do not
+ *     fit report FST_PATH_OUTPUT_FULL and *arc_cursor ends at the arcs the batch needs; call
+ *     again with that capacity.
+ *   - Unlike fst_device_compose_shortest_path the call SYNCHRONISES `stream` (the engine sizes
+ *     its tiers from counts it reads back); it returns with the result complete.
+ *   - fst_last_launch_stats reports engine 8 / 9 as for the host entry; `launches` counts
+ *     the two preparation kernels too. */
+FstError fst_device_compose_shortest_path_lhs(FstHandle b, const FstLhsBatch* d_lhs,
+                                              uint32_t n, const FstBatchOptions* opts,
+                                              const FstDeviceBatch* out, void* stream);
+
 /* Text in, text out: the loop the reference application runs per utterance and stage,
  *   fst_compile_string(bytes) -> fst_compose_frozen_shortest_path -> fst_print_output_string
  * (README.md:177-214, src/string.zig:17-97), for a whole batch with bytes on both sides of
@@ -239,6 +299,10 @@ FstError fst_normalize_text_batch(const FstHandle* stages, uint32_t num_stages,
                                   uint32_t num_strings, const FstBatchOptions* opts,
                                   FstTextResult* out);
 void fst_text_result_free(FstTextResult* r);
+/* Lattices in, text out: the text form of fst_pipeline_lhs_batch (documented there). */
+FstError fst_normalize_lhs_batch(const FstHandle* stages, uint32_t num_stages,
+                                 const FstLhsBatch* lhs,
+                                 const FstBatchOptions* opts, FstTextResult* out);
 
 /* The device-resident pieces (every d_ pointer is device memory on the current device).
  * fst_device_compile_text: d_labels[k] = d_text[k] + 1 for k in [d_offsets[0],

@@ -137,19 +137,33 @@ bool lhs_batch_valid(const FstLhsBatch* L) {
   return true;
 }
 
-FstError lhs_batch_impl(FstHandle b_handle, const FstLhsBatch* lhs, uint32_t n,
-                        const FstBatchOptions* opts, FstBatchResult* out) {
-  std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
-  if (!b) return FST_INVALID_ARG;
-  const uint32_t num = lhs->num_fsts;
-  if (num == 0) {
-    if (!alloc_result(out, 0, 0)) {
-      fst_batch_result_free(out);
-      return FST_OOM;
-    }
-    out->path_offsets[0] = 0;
-    return FST_OK;
+// The empty OK result of a batch of no items.
+FstError empty_result(FstBatchResult* out) {
+  if (!alloc_result(out, 0, 0)) {
+    fst_batch_result_free(out);
+    return FST_OOM;
   }
+  out->path_offsets[0] = 0;
+  return FST_OK;
+}
+FstError empty_result(FstTextResult* out) {
+  if (!alloc_text_result(out, 0, 0)) {
+    fst_text_result_free(out);
+    return FST_OOM;
+  }
+  out->text_offsets[0] = 0;
+  return FST_OK;
+}
+
+// A checked batch of general lhs through `fs` (one stage: the lhs batch entry; several: stage
+// 1 on the lhs, then chain stages on the 1-best output tapes) into a label or a text result.
+// Shards are balanced by arcs + 1 per item.
+template <class R>
+FstError lhs_stages_impl(const Stages& fs, const FstLhsBatch* lhs, uint32_t n,
+                         const FstBatchOptions* opts, R* out, const char* name,
+                         void (*release)(R*)) {
+  const uint32_t num = lhs->num_fsts;
+  if (num == 0) return empty_result(out);
   BatchCall call;
   if (FstError e = call.open(opts); e != FST_OK) return e;
   if (call.semantics != FST_SEM_LAZY && call.semantics != FST_SEM_EAGER) return FST_INVALID_ARG;
@@ -159,8 +173,27 @@ FstError lhs_batch_impl(FstHandle b_handle, const FstLhsBatch* lhs, uint32_t n,
                        lhs->arc_offsets[lhs->state_offsets[i]]) + 1.0;
   const FstError e = run_sharded(
       call.devices, call.nsh, num, cost,
-      [&](Shard& S) { return run_lhs_shard(S, *b, *lhs, n, call.semantics); }, out);
-  return call.close(e, "fst_compose_frozen_shortest_path_lhs_batch", out, fst_batch_result_free);
+      [&](Shard& S) { return run_lhs_pipeline_shard(S, fs, *lhs, n, call.semantics); }, out);
+  return call.close(e, name, out, release);
+}
+
+FstError lhs_batch_impl(FstHandle b_handle, const FstLhsBatch* lhs, uint32_t n,
+                        const FstBatchOptions* opts, FstBatchResult* out) {
+  std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
+  if (!b) return FST_INVALID_ARG;
+  return lhs_stages_impl(Stages{b}, lhs, n, opts, out,
+                         "fst_compose_frozen_shortest_path_lhs_batch", fst_batch_result_free);
+}
+
+// The argument checks of the two lhs pipeline entries (`out` checked and zeroed before): the
+// lhs batch entry's, plus the stages.
+bool lhs_pipeline_args(const FstHandle* stages, uint32_t num_stages, const FstLhsBatch* lhs,
+                       const FstBatchOptions* opts, Stages* fs) {
+  if (!stages || num_stages == 0 || !lhs_batch_valid(lhs) || !flags_ok(opts)) return false;
+  fs->resize(num_stages);
+  for (uint32_t k = 0; k < num_stages; ++k)
+    if (!((*fs)[k] = frozen_get(stages[k]))) return false;
+  return true;
 }
 
 }  // namespace
@@ -277,6 +310,101 @@ FstError fst_compose_frozen_shortest_path_handles_batch(FstHandle b_handle,
                       il.data(), ol.data(),            w.data(),     nx.data()};
   if (!lhs_batch_valid(&L)) return FST_INVALID_ARG;
   return lhs_batch_impl(b_handle, &L, n, opts, out);
+}
+
+FstError fst_pipeline_lhs_batch(const FstHandle* stages, uint32_t num_stages,
+                                const FstLhsBatch* lhs, uint32_t n, const FstBatchOptions* opts,
+                                FstBatchResult* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  Stages fs;
+  if (!lhs_pipeline_args(stages, num_stages, lhs, opts, &fs)) return FST_INVALID_ARG;
+  return lhs_stages_impl(fs, lhs, n, opts, out, "fst_pipeline_lhs_batch", fst_batch_result_free);
+}
+
+FstError fst_normalize_lhs_batch(const FstHandle* stages, uint32_t num_stages,
+                                 const FstLhsBatch* lhs, const FstBatchOptions* opts,
+                                 FstTextResult* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  Stages fs;
+  if (!lhs_pipeline_args(stages, num_stages, lhs, opts, &fs)) return FST_INVALID_ARG;
+  return lhs_stages_impl(fs, lhs, 1, opts, out, "fst_normalize_lhs_batch", fst_text_result_free);
+}
+
+// The device-resident form: d_lhs's arrays are device memory, used in place.  The host reads
+// the two extents (the last state offset, the last arc offset) and nothing else of them; the
+// prepare kernel (DeviceEngine::prepare_lhs) validates the items and derives what
+// run_lhs_shard derives on the host, then the same engine runs.
+FstError fst_device_compose_shortest_path_lhs(FstHandle b_handle, const FstLhsBatch* d_lhs,
+                                              uint32_t n, const FstBatchOptions* opts,
+                                              const FstDeviceBatch* o, void* stream) {
+  if (!o || !d_lhs || !flags_ok(opts)) return FST_INVALID_ARG;
+  const uint32_t num = d_lhs->num_fsts;
+  if (num && (!d_lhs->state_offsets || !d_lhs->start || !d_lhs->arc_offsets))
+    return FST_INVALID_ARG;
+  if (!o->arc_cursor || (num && (!o->status || !o->path_len || !o->path_offset || !o->final_weight)))
+    return FST_INVALID_ARG;
+  const int semantics = opts ? (int)opts->semantics : FST_SEM_LAZY;
+  if (semantics != FST_SEM_LAZY && semantics != FST_SEM_EAGER) return FST_INVALID_ARG;
+  std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
+  if (!b) return FST_INVALID_ARG;
+  if (!gpu_available()) return FST_INVALID_ARG;
+  DeviceRestore_ restore;
+  const int dev = opts && opts->device >= 0 ? opts->device : current_device();
+  if (dev < 0 || hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  DeviceFst* D = b->device(dev);
+  if (!D) return FST_OOM;
+  DeviceEngine::Lease E = DeviceEngine::acquire(dev);
+  if (!E) return FST_INVALID_ARG;
+  const hipStream_t s = E.use((hipStream_t)stream);
+  // every return waits for what the call queued: the engine's workspaces are its own again
+  StreamDrain drain{{s}};
+  LhsPrepIn in{};
+  in.num = num;
+  in.state_offsets = d_lhs->state_offsets;
+  in.start = d_lhs->start;
+  in.final_w = d_lhs->final_weights;
+  in.arc_offsets = d_lhs->arc_offsets;
+  in.arc_ol = d_lhs->olabels;
+  in.arc_w = d_lhs->weights;
+  in.arc_next = d_lhs->nextstates;
+  // the extents of the caller's arrays, trusted (fst_batch.h): the prepare kernel checks
+  // every other offset against them
+  if (num) {
+    if (!read_u64(&in.total_states, d_lhs->state_offsets + num, s)) return FST_OOM;
+    if (!read_u64(&in.total_arcs, d_lhs->arc_offsets + in.total_states, s)) return FST_OOM;
+  }
+  if ((in.total_states && !d_lhs->final_weights) ||
+      (in.total_arcs &&
+       (!d_lhs->ilabels || !d_lhs->olabels || !d_lhs->weights || !d_lhs->nextstates)))
+    return FST_INVALID_ARG;
+  LhsPrepared p;
+  if (E->prepare_lhs(*D, in, s, &p) != hipSuccess) return FST_OOM;
+  if (p.max_outdeg >= (1u << 30)) return FST_OOM;  // the lazy per-pop table is 2 * deg + 2 entries
+  ChainInput ci{};
+  ci.lhs_desc = p.desc;
+  ci.num_strings = num;
+  GraphInput g{};
+  g.state_off = p.state_off;
+  g.final_w = d_lhs->final_weights;
+  g.arc_w = d_lhs->weights;
+  g.arc_il = d_lhs->ilabels;
+  g.arc_ol = d_lhs->olabels;
+  g.arc_next = d_lhs->nextstates;
+  g.start = kNoState;
+  g.max_outdeg = p.max_outdeg;
+  LaunchStats st;
+  LhsRoute route;
+  if (E->run_lhs_batch(*D, ci, g, n, semantics, p.items_nonneg, p.num_nonneg, p.items_replay,
+                       p.num_replay, dev_out(o), s, &st, &route) != hipSuccess)
+    return FST_OOM;
+  st.launches += p.launches;
+  t_last_stats = st;
+  // (run_lhs_batch waited for its last tier: with stats it ends on an event of the stream;
+  // an empty batch queued one memset, which the drain still waits for)
+  drain.done = num != 0;
+  return FST_OK;
 }
 
 FstError fst_device_project_output(const FstDeviceBatch* o, uint32_t num_strings,

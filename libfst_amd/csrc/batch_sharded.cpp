@@ -1,6 +1,7 @@
 // batch_sharded.cpp -- host batches through the path arena: one engine run with arena
 // growth, the shards of a call and their result sinks (labels, text), the pipelined
-// one-device batch, and the per-shard compute steps (pipeline stages, text, general lhs).
+// one-device batch, and the per-shard compute steps (pipeline stages, text, general lhs, and
+// pipelines on a general first stage).
 #include <cmath>
 #include <condition_variable>
 
@@ -167,46 +168,82 @@ FstError shard_text_download(Shard& S, FstTextResult* out, uint64_t byte_base) {
   return FST_OK;
 }
 
-// The stages of one shard on device inputs (labels `lab`, offsets `off`, in_total labels).
-FstError run_pipeline_stages(Shard& S, const Stages& fs, std::unique_ptr<DevBuf> lab,
-                             std::unique_ptr<DevBuf> off, uint64_t in_total, uint32_t max_len,
-                             uint32_t n, int semantics) {
+// One chain stage of a shard on device inputs: S.keep = its outputs (`h`: the statuses, one
+// pinned block for all the stages of a shard).
+FstError run_chain_stage(Shard& S, FrozenFst& f, const DevBuf& lab, const DevBuf& off,
+                         uint64_t in_total, uint32_t max_len, uint32_t n, int semantics,
+                         HostPaths* h) {
+  const uint32_t num_strings = S.s1 - S.s0;
+  DeviceFst* D = f.device(S.dev);
+  if (!D) return FST_OOM;
+  ChainInput in{{(const uint32_t*)lab.p}, (const uint64_t*)off.p, num_strings, max_len};
+  S.keep.reset();
+  FstError e = run_chain_batch_dev(S.E, *D, in, in_total, n, semantics, h, &S.keep);
+  if (e != FST_OK) return e;
+  return S.keep ? FST_OK : FST_OOM;  // run_chain_batch_dev sets it on FST_OK
+}
+
+// S.fail of a shard whose first stage is about to run or has just finished: no failure yet.
+FstError clear_stage_failures(Shard& S) {
+  const uint32_t num_strings = S.s1 - S.s0;
+  S.fail = std::make_unique<DevBuf>(num_strings * 4ull);  // first failing stage per string
+  if (!S.fail->p ||
+      hipMemsetAsync(S.fail->p, 0, num_strings * 4ull, S.E.stream()) != hipSuccess)
+    return FST_OOM;
+  return FST_OK;
+}
+
+// The stages [first, fs.size()) of one shard, from a finished stage: S.keep holds stage
+// first - 1's outputs (whatever entry produced them: a chain stage, a general-lhs batch) and
+// S.fail the failures so far.  Each stage's 1-best output tape is projected into the next
+// stage's chain inputs on the device.
+FstError run_stages_after(Shard& S, const Stages& fs, size_t first, uint32_t n, int semantics,
+                          HostPaths* h) {
   DeviceEngine::Lease& E = S.E;
-  const int dev = S.dev;
   const uint32_t num_strings = S.s1 - S.s0;
   const hipStream_t stream = E.stream();
-  S.fail = std::make_unique<DevBuf>(num_strings * 4ull);  // first failing stage per string
-  if (!S.fail->p || hipMemsetAsync(S.fail->p, 0, num_strings * 4ull, stream) != hipSuccess)
-    return FST_OOM;
-  HostPaths h;
-  for (size_t k = 0; k < fs.size(); ++k) {
-    DeviceFst* D = fs[k]->device(dev);
-    if (!D) return FST_OOM;
-    ChainInput in{(const uint32_t*)lab->p, (const uint64_t*)off->p, num_strings, max_len};
-    S.keep.reset();
-    FstError e = run_chain_batch_dev(E, *D, in, in_total, n, semantics, &h, &S.keep);
-    if (e != FST_OK) return e;
-    if (!S.keep) return FST_OOM;  // run_chain_batch_dev sets it on FST_OK
-    if (k + 1 == fs.size()) break;
-    // project this stage's outputs into the next stage's inputs, on the device
+  for (size_t k = first; k < fs.size(); ++k) {
+    // project the finished stage's outputs into this stage's inputs, on the device
     unsigned long long used = 0;
     if (!read_u64(&used, S.keep->v.cursor, stream)) return FST_OOM;
-    auto nlab = std::make_unique<DevBuf>((used + num_strings) * 4);
-    auto noff = std::make_unique<DevBuf>((num_strings + 1ull) * 8);
+    DevBuf lab((used + num_strings) * 4), off((num_strings + 1ull) * 8);
     DevBuf pst(num_strings * 4ull);
-    if (!nlab->p || !noff->p || !pst.p) return FST_OOM;
-    if (E->project_output(S.keep->v, num_strings, (uint32_t*)nlab->p, (uint64_t*)noff->p,
+    if (!lab.p || !off.p || !pst.p) return FST_OOM;
+    // a failure below drains the stream before the three go back to the pool
+    StreamDrain drain{{stream}};
+    uint32_t max_len = 0;
+    if (E->project_output(S.keep->v, num_strings, (uint32_t*)lab.p, (uint64_t*)off.p,
                           (int32_t*)pst.p, &max_len, stream) != hipSuccess ||
         E->merge_status((int32_t*)S.fail->p, (const int32_t*)pst.p, num_strings, stream) !=
             hipSuccess)
       return FST_OOM;
     // (synchronises: pst may go back to the pool)
-    if (!read_u64(&in_total, (uint64_t*)noff->p + num_strings, stream)) return FST_OOM;
-    lab = std::move(nlab);
-    off = std::move(noff);
+    uint64_t in_total = 0;
+    if (!read_u64(&in_total, (uint64_t*)off.p + num_strings, stream)) return FST_OOM;
     if (t_prof) t_prof->lap(4);
+    // (the stage synchronises the stream before lab and off go back to the pool)
+    if (FstError e = run_chain_stage(S, *fs[k], lab, off, in_total, max_len, n, semantics, h);
+        e != FST_OK)
+      return e;
+    drain.done = true;
   }
   return FST_OK;
+}
+
+// The stages of one shard on device inputs (labels `lab`, offsets `off`, in_total labels).
+FstError run_pipeline_stages(Shard& S, const Stages& fs, std::unique_ptr<DevBuf> lab,
+                             std::unique_ptr<DevBuf> off, uint64_t in_total, uint32_t max_len,
+                             uint32_t n, int semantics) {
+  if (FstError e = clear_stage_failures(S); e != FST_OK) return e;
+  HostPaths h;
+  if (FstError e = run_chain_stage(S, *fs[0], *lab, *off, in_total, max_len, n, semantics, &h);
+      e != FST_OK)
+    return e;
+  // (the stage synchronised the stream: its inputs go back to the pool before the next
+  // stage's are allocated)
+  lab.reset();
+  off.reset();
+  return run_stages_after(S, fs, 1, n, semantics, &h);
 }
 
 }  // namespace
@@ -648,6 +685,23 @@ FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n,
                                   (const uint32_t*)(p + o_lb), n_b, v, stream, st, &route);
       },
       &h, &S.keep);
+}
+
+// One shard of a pipeline on a general first stage: stage 1 is run_lhs_shard as it stands,
+// then the chain stages from its finished outputs (the projection step of
+// run_pipeline_stages); S.keep = the last stage's outputs, S.fail = the first failing stage.
+FstError run_lhs_pipeline_shard(Shard& S, const Stages& fs, const FstLhsBatch& L, uint32_t n,
+                                int semantics) {
+  if (FstError e = run_lhs_shard(S, *fs[0], L, n, semantics); e != FST_OK) return e;
+  if (fs.size() == 1) return FST_OK;
+  if (!S.keep) return FST_OOM;  // run_arena sets it on FST_OK
+  HostPaths h;  // (the statuses of each stage)
+  // every failure return drains the stream before h, S.fail and the stages' buffers go
+  StreamDrain drain{{S.E.stream()}};
+  FstError e = clear_stage_failures(S);
+  if (e == FST_OK) e = run_stages_after(S, fs, 1, n, semantics, &h);
+  drain.done = e == FST_OK;  // (the last stage synchronised it)
+  return e;
 }
 
 }  // namespace fstamd::host

@@ -399,6 +399,11 @@ enum Scratch : size_t {
   kItems4,
   kLpBack,
   kItems5,
+  kLhsPrepDesc,
+  kLhsPrepSoff,
+  kLhsPrepNonneg,
+  kLhsPrepReplay,
+  kLhsPrepTotals,
   kNumScratch
 };
 
@@ -2840,6 +2845,56 @@ hipError_t DeviceEngine::run_lhs_batch(const DeviceFst& rhs, const ChainInput& i
                    num, r.t[0], r.t[1], r.t[2], r.t[3], r.t[4]);
   }
   if (route) *route = r;
+  return hipSuccess;
+}
+
+hipError_t DeviceEngine::prepare_lhs(const DeviceFst& rhs, LhsPrepIn in, hipStream_t stream,
+                                     LhsPrepared* prepared) {
+  HIP_TRY(hipSetDevice(dev_));
+  *prepared = LhsPrepared();
+  const uint32_t num = in.num;
+  if (num == 0) return hipStreamSynchronize(stream);
+  in.base_flags = (rhs.nan ? kLhsNaN : 0u) | (rhs.nonneg ? 0u : kLhsReplay);
+  LhsPrepOut out{};
+  out.desc = (LhsDesc*)scratch(kLhsPrepDesc, (size_t)num * sizeof(LhsDesc));
+  // one extra offset word per item (lhs_item: the item's words start at state_base + i)
+  out.state_off = (uint32_t*)scratch(kLhsPrepSoff, (size_t)(in.total_states + num) * 4);
+  out.totals = (uint32_t*)scratch(kLhsPrepTotals, kLhsPrepTotalsWords * 4);
+  uint32_t* nonneg = (uint32_t*)scratch(kLhsPrepNonneg, (size_t)num * 4);
+  uint32_t* replay = (uint32_t*)scratch(kLhsPrepReplay, (size_t)num * 4);
+  if (!out.desc || !out.state_off || !out.totals || !nonneg || !replay)
+    return hipErrorOutOfMemory;
+  // one wave per item in flight, a few per SIMD: the kernel streams the batch once
+  uint32_t grid = (uint32_t)std::min<uint64_t>(num, (uint64_t)num_cus_ * 32);
+  grid = std::max<uint32_t>(1, std::min<uint32_t>(grid, grid_cap("FSTAMD_GRAPH_GRID")));
+  uint32_t totals[kLhsPrepTotalsWords] = {};
+  for (int pass = 0; pass < 2; ++pass) {
+    HIP_TRY(hipMemsetAsync(out.totals, 0, sizeof(totals), stream));
+    HIP_TRY(launch_lhs_prepare(in, out, grid, stream));
+    HIP_TRY(launch_lhs_lists(out.desc, num, nonneg, replay, out.totals, stream));
+    HIP_TRY(copy_sync(totals, out.totals, sizeof(totals), hipMemcpyDeviceToHost, stream));
+    prepared->launches += 2;
+    // state_offsets decreases somewhere: items that pass their own checks may still overlap
+    // in state_off (kernels/lhs_prepare.hpp), so no item of such a batch is run.  The second
+    // pass marks them all invalid without reading them.
+    if (totals[4] == 0 || (in.base_flags & kLhsInvalid)) break;
+    in.base_flags |= kLhsInvalid;
+  }
+  if ((uint64_t)totals[0] + totals[1] != num) return hipErrorUnknown;  // (the lists' invariant)
+  if (totals[4] != 0 && totals[3] != num) return hipErrorUnknown;      // (the second pass's)
+  prepared->desc = out.desc;
+  prepared->state_off = out.state_off;
+  prepared->items_nonneg = nonneg;
+  prepared->items_replay = replay;
+  prepared->num_nonneg = totals[0];
+  prepared->num_replay = totals[1];
+  prepared->max_outdeg = totals[2];
+  prepared->invalid = totals[3];
+  if (std::getenv("FSTAMD_ROUTE_LOG"))
+    std::fprintf(stderr,
+                 "[libfst_amd route] lhs prepare: items %u invalid %u max out-degree %u | "
+                 "nonneg %u replay %u | decreasing state offsets %u\n",
+                 num, totals[3], totals[2], totals[0], totals[1], totals[4]);
   return hipSuccess;
 }
 

@@ -280,6 +280,9 @@ constexpr uint32_t kLhsReplay = 1u;  // eager: a weight that is negative, -0.0 o
                                      // the exact heap replay (sp_replay), not the fixpoint
 constexpr uint32_t kLhsNaN = 2u;     // a NaN weight (in the item or the rhs): UNSUPPORTED
 constexpr uint32_t kLhsEpsOut = 4u;  // some arc has output epsilon
+constexpr uint32_t kLhsInvalid = 8u; // the device-resident entry's prepare kernel: the item
+                                     // failed validation (it also carries kLhsNaN, the bit the
+                                     // kernels turn into UNSUPPORTED; this one is for the log)
 struct GraphInput {       // CSR of a MutableFst lhs, arcs in insertion order
   const uint32_t* state_off;   // [ns + 1]
   const uint32_t* arc_il;
@@ -392,6 +395,47 @@ hipError_t launch_lhs_lazy(const RhsView& rhs, const ChainInput& in, const Graph
                            uint32_t n_best, unsigned int* next_item, const uint32_t* items,
                            uint32_t num_items, const LazyWs& ws, const BatchOutDev& out,
                            uint32_t grid, hipStream_t stream);
+// On-device preparation of a device-resident batch (kernels/lhs_prepare.hpp; lhs_batch.hip
+// holds the instances).  In: the caller's arrays in FstLhsBatch's layout, all device memory,
+// and their two extents as the host read them.  Out: descriptors, local arc offsets
+// (total_states + num words), the two eager item lists in ascending item order, and five
+// totals: [0] non-negative items, [1] replay items, [2] largest out-degree, [3] invalid items,
+// [4] items i with state_offsets[i] > state_offsets[i + 1] (not zero: the whole batch is
+// invalid, kernels/lhs_prepare.hpp).
+constexpr uint32_t kLhsPrepTotalsWords = 5;
+struct LhsPrepIn {
+  const uint64_t* state_offsets;  // [num + 1]
+  const uint32_t* start;          // [num]
+  const double* final_w;          // [total_states]
+  const uint64_t* arc_offsets;    // [total_states + 1]
+  const uint32_t* arc_ol;         // [total_arcs]
+  const double* arc_w;
+  const uint32_t* arc_next;
+  uint64_t total_states;
+  uint64_t total_arcs;
+  uint32_t num;
+  uint32_t base_flags;            // the rhs's share of every item's flags; with kLhsInvalid
+                                  // every item is invalid and none is read
+};
+struct LhsPrepOut {
+  LhsDesc* desc;
+  uint32_t* state_off;
+  uint32_t* totals;  // [kLhsPrepTotalsWords], zeroed before the launch
+};
+hipError_t launch_lhs_prepare(const LhsPrepIn& in, const LhsPrepOut& out, uint32_t grid,
+                              hipStream_t stream);
+hipError_t launch_lhs_lists(const LhsDesc* desc, uint32_t num, uint32_t* list_nonneg,
+                            uint32_t* list_replay, uint32_t* totals, hipStream_t stream);
+// What DeviceEngine::prepare_lhs leaves in the engine's workspaces for run_lhs_batch.
+struct LhsPrepared {
+  const LhsDesc* desc = nullptr;
+  const uint32_t* state_off = nullptr;
+  const uint32_t* items_nonneg = nullptr;
+  const uint32_t* items_replay = nullptr;
+  uint32_t num_nonneg = 0, num_replay = 0, max_outdeg = 0, invalid = 0;
+  uint32_t launches = 0;
+};
+
 // What a batch of general lhs took which way (FSTAMD_ROUTE_LOG, tests): items that entered
 // each tier.  Eager: t[0..3] = tiny128, tiny256, tier 0, tiers 1+ (summed); replay = items on
 // the heap-replay route (they appear in t[2..3] too).  Lazy: t[k] = items that entered the
@@ -492,6 +536,15 @@ class DeviceEngine {
                            uint32_t num_nonneg, const uint32_t* items_replay,
                            uint32_t num_replay, const BatchOutDev& out, hipStream_t stream,
                            LaunchStats* stats, LhsRoute* route);
+  // The inputs of run_lhs_batch for a batch that is already in device memory
+  // (fst_device_compose_shortest_path_lhs): lhs_prepare_kernel validates every item against
+  // in.total_states / total_arcs and writes descriptors, local arc offsets and flags into the
+  // engine's workspaces (kinds of their own: run_lhs_batch uses the others in the same call);
+  // lhs_lists_kernel builds the two eager item lists; one small D2H brings the totals back.
+  // A batch whose state_offsets decrease somewhere is prepared a second time with every item
+  // invalid.  Synchronises `stream`.  in.base_flags is set here from the rhs.
+  hipError_t prepare_lhs(const DeviceFst& rhs, LhsPrepIn in, hipStream_t stream,
+                         LhsPrepared* prepared);
   // fst_compose_frozen: the whole lattice of one general lhs (kernels/eager_bfs.hpp), on
   // `stream` (synchronised: the lattice is downloaded).
   hipError_t compose_lattice(const DeviceFst& rhs, const GraphInput& lhs, HostLattice* lat,

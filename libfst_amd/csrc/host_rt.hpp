@@ -203,6 +203,10 @@ FstError run_pipeline_shard(Shard& S, const Stages& fs, const uint32_t* labels,
 FstError run_text_shard(Shard& S, const Stages& fs, const uint8_t* text, const uint64_t* offsets,
                         int semantics);
 FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n, int semantics);
+// ... and a pipeline on a general first stage: run_lhs_shard on fs[0], then the chain stages
+// fs[1 ..] on its 1-best output tapes (S.fail: the first failing stage, when there are several).
+FstError run_lhs_pipeline_shard(Shard& S, const Stages& fs, const FstLhsBatch& L, uint32_t n,
+                                int semantics);
 
 // ---- c_api.cpp: a chain batch from host arrays on the engine `E` leases; fills `h` in input
 // order (small batches in one block, see run_small_batch), or keeps the device outputs ----

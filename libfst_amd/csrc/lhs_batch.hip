@@ -3,12 +3,14 @@
 // 256-thread workgroup) takes one lhs of the batch at a time: it reads the item's 32-B
 // descriptor, forms the GraphInput the single-lhs code takes (device_common.hpp lhs_item) and
 // runs that code unchanged.  DeviceEngine::run_lhs_batch (device_engine.hip) drives the tiers.
+// Also the two kernels that prepare a device-resident batch for it (kernels/lhs_prepare.hpp).
 #include <algorithm>
 
 #define FSTAMD_BFS_TEMPLATES_ONLY  // device_engine.hip holds the non-template kernels
 #include "device_engine.hpp"
 #include "kernels/eager_bfs.hpp"
 #include "kernels/lazy_wave.hpp"
+#include "kernels/lhs_prepare.hpp"
 
 namespace fstamd {
 
@@ -51,6 +53,19 @@ hipError_t launch_lhs_lazy(const RhsView& rhs, const ChainInput& in, const Graph
                            uint32_t grid, hipStream_t stream) {
   lazy_wave_kernel<kLhsBatch><<<grid, 64, 0, stream>>>(rhs, in, lhs, n_best, next_item, items,
                                                        num_items, ws, out);
+  return hipGetLastError();
+}
+
+// The device-resident entry's preparation (kernels/lhs_prepare.hpp).
+hipError_t launch_lhs_prepare(const LhsPrepIn& in, const LhsPrepOut& out, uint32_t grid,
+                              hipStream_t stream) {
+  lhs_prepare_kernel<<<grid, 64, 0, stream>>>(in, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_lhs_lists(const LhsDesc* desc, uint32_t num, uint32_t* list_nonneg,
+                            uint32_t* list_replay, uint32_t* totals, hipStream_t stream) {
+  lhs_lists_kernel<<<1, kLhsListsWG, 0, stream>>>(desc, num, list_nonneg, list_replay, totals);
   return hipGetLastError();
 }
 

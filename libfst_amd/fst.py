@@ -127,6 +127,15 @@ SIGNATURES = {
                   C.POINTER(FstBatchResult)]),
     "fst_compose_frozen_shortest_path_handles_batch": (
         C.c_int, [_u64, _P, _u32, _u32, C.POINTER(FstBatchOptions), C.POINTER(FstBatchResult)]),
+    "fst_pipeline_lhs_batch": (
+        C.c_int, [_P, _u32, C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstBatchResult)]),
+    "fst_normalize_lhs_batch": (
+        C.c_int, [_P, _u32, C.POINTER(FstLhsBatch), C.POINTER(FstBatchOptions),
+                  C.POINTER(FstTextResult)]),
+    "fst_device_compose_shortest_path_lhs": (
+        C.c_int, [_u64, C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstDeviceBatch), _P]),
     "fst_device_compose_shortest_path": (
         C.c_int, [_u64, _P, _P, _u32, _u32, _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceBatch), _P]),
@@ -452,6 +461,39 @@ def compose_frozen_shortest_path_lhs_batch(b: Fst, lhs: LhsBatch, n: int = 1,
     if rc != FST_OK:
         raise RuntimeError(f"fst_compose_frozen_shortest_path_lhs_batch failed: {rc}")
     return _take_result(res, len(lhs))
+
+
+def pipeline_lhs_batch(stages, lhs: LhsBatch, n: int = 1, semantics: int = FST_SEM_LAZY,
+                       devices=None, shards: int = 0, device: int = -1) -> BatchResult:
+    """A pipeline on a general first stage (fst_pipeline_lhs_batch): stage 1 as
+    compose_frozen_shortest_path_lhs_batch, every later stage on the previous stage's 1-best
+    output tape as pipeline_batch; the last stage's paths."""
+    stages = [stages] if isinstance(stages, Fst) else list(stages)
+    hs = (C.c_uint64 * max(len(stages), 1))(*[s.h for s in stages])
+    opts = batch_options(device, semantics, devices, shards)
+    res = FstBatchResult()
+    cs = lhs.c_struct()
+    rc = lib().fst_pipeline_lhs_batch(hs, len(stages), C.byref(cs), n, C.byref(opts),
+                                      C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_pipeline_lhs_batch failed: {rc}")
+    return _take_result(res, len(lhs))
+
+
+def normalize_lhs_batch(stages, lhs: LhsBatch, semantics: int = FST_SEM_LAZY, devices=None,
+                        shards: int = 0, device: int = -1) -> TextResult:
+    """Lattices in, text out (fst_normalize_lhs_batch): the same pipeline with the last
+    stage's 1-best output tape printed on the device, as normalize_text_batch prints it."""
+    stages = [stages] if isinstance(stages, Fst) else list(stages)
+    hs = (C.c_uint64 * max(len(stages), 1))(*[s.h for s in stages])
+    opts = batch_options(device, semantics, devices, shards)
+    res = FstTextResult()
+    cs = lhs.c_struct()
+    rc = lib().fst_normalize_lhs_batch(hs, len(stages), C.byref(cs), C.byref(opts),
+                                       C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_normalize_lhs_batch failed: {rc}")
+    return _take_text(res)
 
 
 def compose_frozen_shortest_path_handles_batch(b: Fst, fsts, n: int = 1,
