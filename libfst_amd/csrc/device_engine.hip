@@ -220,6 +220,14 @@ static DeviceFst* finish_device(DeviceFst* d, const FrozenFst& f) {
                                                                   : d->perm[h.start_state];
   d->view = RhsView{d->span, d->final_w, d->il,       d->rec,     d->sspan,
                     ns,      na,         start,        max_span,   jb, jf, d->sspan + ns};
+  if (std::getenv("FSTAMD_ROUTE_LOG")) {  // one line per device copy: which ids it got
+    uint32_t moved = 0;
+    for (uint32_t i = 0; i < (uint32_t)d->perm.size(); ++i) moved += d->perm[i] != i;
+    std::fprintf(stderr,
+                 "[libfst_amd route] rhs mirror: states %u arcs %u, renumbered %s (moved %u), "
+                 "jump fwd %u back %u\n",
+                 ns, na, d->perm.empty() ? "no" : "yes", moved, jf, jb);
+  }
   d->has_eps = f.has_epsilon_input();
   d->nonneg = f.weights_nonnegative();
   d->nan = f.has_nan_weight();

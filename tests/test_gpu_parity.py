@@ -14,6 +14,7 @@ import pytest
 
 import libfst_amd as F
 import oracle_ffi as O
+from renumber_model import scattered
 
 pytestmark = pytest.mark.gpu
 
@@ -293,17 +294,6 @@ def test_single_call_chain_route(rhs_kind):
 # ---------------------------------------------------------------------------------------
 # an rhs with scattered state ids (device renumbering, device_engine.hip bfs_renumbering)
 # ---------------------------------------------------------------------------------------
-
-def scattered(f: O.Fst, seed) -> O.Fst:
-    perm = np.random.default_rng(seed).permutation(f.num_states)
-    g = O.Fst(start=int(perm[f.start]), finals=[0.0] * f.num_states,
-              arcs=[[] for _ in range(f.num_states)])
-    for s, fw in enumerate(f.finals):
-        g.finals[int(perm[s])] = fw
-    for s, al in enumerate(f.arcs):
-        g.arcs[int(perm[s])] = [(a, b, w, int(perm[d])) for (a, b, w, d) in al]
-    return g
-
 
 @pytest.mark.parametrize("sem", [EAGER, LAZY])
 def test_scattered_state_ids_take_the_pull_tiers(sem):
