@@ -249,6 +249,72 @@ FstError fst_device_compose_shortest_path_lhs(FstHandle b, const FstLhsBatch* d_
                                               uint32_t n, const FstBatchOptions* opts,
                                               const FstDeviceBatch* out, void* stream);
 
+/* Lattices out: fst_compose_frozen for a whole batch.  Item i of the result is, bit for bit,
+ * the MutableFst fst_compose_frozen(a_i, b) returns (src/ops/compose.zig:29-198): states in
+ * the reference's BFS ids, arcs of a state in compose order, arc weights times(w_lhs, w_rhs),
+ * final weights times(fw1, fw2) (+inf: not final), start 0 when the lattice has states, no
+ * trimming.  For the chain entry a_i is the fst_compile_string-style chain of string i's
+ * labels (zero labels: the one-state final acceptor).  The result is an FstLhsBatch: &r.fsts is
+ * a valid argument of every lhs batch entry, so
+ *   compose(project_output(compose(a, tagger)), verbalizer)
+ * is two library calls on batches, and the optimum over both stages is kept.
+ * With FST_LATTICE_PROJECT_OUTPUT the only difference is ilabels[k] = olabels[k]
+ * (src/ops/project.zig, .output).
+ * Statuses: FST_PATH_OK is a lattice, and also the reference's empty FST when the lhs or the
+ * rhs has no start (zero states, start = FST_NO_STATE).  A NaN weight in the item or the rhs:
+ * FST_PATH_UNSUPPORTED, as the lhs batch entry reports it (the single call composes NaNs; this
+ * is a documented difference).  FST_PATH_OVERFLOW: no engine tier holds the item (the single
+ * call returns FST_INVALID_HANDLE there).  FST_PATH_INTERNAL: the watchdog.  Every non-OK item
+ * owns zero states and has start = FST_NO_STATE.  opts->semantics is ignored.
+ * Checked on the host before any device work, each FST_INVALID_ARG with *out zeroed: what
+ * fst_compose_frozen_shortest_path_lhs_batch checks of an lhs batch (the same validator) /
+ * what fst_compose_frozen_shortest_path_batch checks of labels and offsets, unknown bits in
+ * lattice_flags or opts->flags, an invalid handle.  Zero items give an empty OK result with
+ * state_offsets = {0} and arc_offsets = {0}.  FST_BATCH_DEVICES shards as the 1-best entries
+ * do (fst_chain_cost per chain, arcs + 1 per lhs); a sharded result is byte-identical to a
+ * one-shard run.  The result lives in pooled pinned blocks until fst_lattice_batch_free. */
+typedef struct {
+    FstLhsBatch fsts;        /* the lattices; &r.fsts is a valid argument of every lhs batch entry */
+    int32_t* status;         /* [fsts.num_fsts] FstPathStatus */
+    uint64_t total_states, total_arcs;
+} FstLatticeBatch;
+
+#define FST_LATTICE_PROJECT_OUTPUT 1u   /* every arc's ilabel := its olabel (project.zig, .output) */
+
+FstError fst_compose_frozen_batch(FstHandle b, const uint32_t* labels, const uint64_t* offsets,
+                                  uint32_t num_strings, uint32_t lattice_flags,
+                                  const FstBatchOptions* opts, FstLatticeBatch* out);
+FstError fst_compose_frozen_lhs_batch(FstHandle b, const FstLhsBatch* lhs, uint32_t lattice_flags,
+                                      const FstBatchOptions* opts, FstLatticeBatch* out);
+void fst_lattice_batch_free(FstLatticeBatch* r);
+
+/* The device-resident form, chains in and lattices out, so that a cascade never leaves the
+ * device.  Every pointer in `out` is device memory on opts->device, in FstLhsBatch's layout: a
+ * host-side FstLhsBatch holding those pointers goes straight into
+ * fst_device_compose_shortest_path_lhs.  The call SYNCHRONISES `stream` (the tier ladder reads
+ * counts back).  needed (host memory) receives the states and arcs the batch needs; when
+ * either exceeds its capacity only `status` and `needed` are defined and nothing past a
+ * capacity is written: call again with larger arrays (the pattern of fst_device_emit_text).
+ * FST_INVALID_ARG: a null out / needed / d_offsets or array, unknown flags, an invalid
+ * handle.  The host cannot read d_offsets (it reads the first and the last entry, to size its
+ * arena): they are TRUSTED, as fst_device_compose_shortest_path trusts them -- the caller
+ * guarantees d_offsets[0 .. num_strings] is non-decreasing and that d_labels holds
+ * d_offsets[num_strings] labels; nothing is checked per string, and max_len is a hint, not
+ * enforced.  num_strings == 0 is valid: needed = {0, 0}, state_offsets[0] = 0 and
+ * arc_offsets[0] = 0 are written, status and start may then be NULL.
+ * fst_last_launch_stats reports engine 10. */
+typedef struct {
+    int32_t* status; uint64_t* state_offsets; uint32_t* start;   /* [num], [num + 1], [num] */
+    double* final_weights; uint64_t* arc_offsets;                /* [state_capacity], [state_capacity + 1] */
+    uint32_t* ilabels; uint32_t* olabels; double* weights; uint32_t* nextstates;  /* [arc_capacity] */
+    uint64_t state_capacity, arc_capacity;
+} FstDeviceLattices;
+
+FstError fst_device_compose_frozen(FstHandle b, const uint32_t* d_labels, const uint64_t* d_offsets,
+                                   uint32_t num_strings, uint32_t max_len, uint32_t lattice_flags,
+                                   const FstBatchOptions* opts, const FstDeviceLattices* out,
+                                   uint64_t needed[2], void* stream);
+
 /* Text in, text out: the loop the reference application runs per utterance and stage,
  *   fst_compile_string(bytes) -> fst_compose_frozen_shortest_path -> fst_print_output_string
  * (README.md:177-214, src/string.zig:17-97), for a whole batch with bytes on both sides of
@@ -343,7 +409,8 @@ typedef struct {
                                    5 = lazy dense replay, 6 = shortest-path heap replay,
                                    7 = lazy pull tier,
                                    8 = lhs batch, lazy (hashed replay, one wave per lhs),
-                                   9 = lhs batch, eager (general BFS tiers, 1-best in kernel) */
+                                   9 = lhs batch, eager (general BFS tiers, 1-best in kernel),
+                                   10 = lattice batch (general BFS tiers, lattice emission) */
     uint32_t grid;              /* workgroups of the dominant kernel */
 } FstLaunchStats;
 FstError fst_last_launch_stats(FstLaunchStats* out);

@@ -11,4 +11,6 @@ from .fst import (  # noqa: F401
     compose_frozen_shortest_path, coalescer_state, compose_frozen_shortest_path_batch,
     last_launch_stats, lib, normalize_text_batch, pipeline_batch, shortest_path,
     FstLhsBatch, LhsBatch, compose_frozen_shortest_path_lhs_batch,
-    compose_frozen_shortest_path_handles_batch, normalize_lhs_batch, pipeline_lhs_batch)
+    compose_frozen_shortest_path_handles_batch, normalize_lhs_batch, pipeline_lhs_batch,
+    FST_LATTICE_PROJECT_OUTPUT, FST_PATH_INTERNAL, FstDeviceLattices, FstLatticeBatch,
+    LatticeBatch, compose_frozen_batch, compose_frozen_lhs_batch)

@@ -155,6 +155,18 @@ FstError empty_result(FstTextResult* out) {
   return FST_OK;
 }
 
+// ... of the lattice entries: no item, state_offsets = {0}, arc_offsets = {0}.
+FstError empty_result(FstLatticeBatch* out) {
+  if (!alloc_lattice_result(out, 0, 0, 0)) {
+    fst_lattice_batch_free(out);
+    return FST_OOM;
+  }
+  const_cast<uint64_t*>(out->fsts.state_offsets)[0] = 0;
+  const_cast<uint64_t*>(out->fsts.arc_offsets)[0] = 0;
+  return FST_OK;
+}
+bool lattice_flags_ok(uint32_t f) { return !(f & ~FST_LATTICE_PROJECT_OUTPUT); }
+
 // A checked batch of general lhs through `fs` (one stage: the lhs batch entry; several: stage
 // 1 on the lhs, then chain stages on the 1-best output tapes) into a label or a text result.
 // Shards are balanced by arcs + 1 per item.
@@ -330,6 +342,134 @@ FstError fst_normalize_lhs_batch(const FstHandle* stages, uint32_t num_stages,
   Stages fs;
   if (!lhs_pipeline_args(stages, num_stages, lhs, opts, &fs)) return FST_INVALID_ARG;
   return lhs_stages_impl(fs, lhs, 1, opts, out, "fst_normalize_lhs_batch", fst_text_result_free);
+}
+
+// ---- Lattices out (fst_compose_frozen for a batch) -------------------------------------
+
+FstError fst_compose_frozen_batch(FstHandle b_handle, const uint32_t* labels,
+                                  const uint64_t* offsets, uint32_t num_strings,
+                                  uint32_t lattice_flags, const FstBatchOptions* opts,
+                                  FstLatticeBatch* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!offsets || (!labels && num_strings && offsets[num_strings] != offsets[0]))
+    return FST_INVALID_ARG;
+  if (!offsets_monotone(offsets, num_strings) || !flags_ok(opts) ||
+      !lattice_flags_ok(lattice_flags))
+    return FST_INVALID_ARG;
+  std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
+  if (!b) return FST_INVALID_ARG;
+  if (num_strings == 0) return empty_result(out);
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  const FstError e = run_sharded(
+      call.devices, call.nsh, num_strings, chain_costs(*b, offsets, num_strings, call.nsh),
+      [&](Shard& S) {
+        return run_lattice_chain_shard(S, *b, labels, offsets + S.s0, lattice_flags);
+      },
+      out);
+  return call.close(e, "fst_compose_frozen_batch", out, fst_lattice_batch_free);
+}
+
+FstError fst_compose_frozen_lhs_batch(FstHandle b_handle, const FstLhsBatch* lhs,
+                                      uint32_t lattice_flags, const FstBatchOptions* opts,
+                                      FstLatticeBatch* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!lhs_batch_valid(lhs) || !flags_ok(opts) || !lattice_flags_ok(lattice_flags))
+    return FST_INVALID_ARG;
+  std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
+  if (!b) return FST_INVALID_ARG;
+  const uint32_t num = lhs->num_fsts;
+  if (num == 0) return empty_result(out);
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  std::vector<double> cost(call.nsh > 1 ? num : 0);
+  for (size_t i = 0; i < cost.size(); ++i)
+    cost[i] = (double)(lhs->arc_offsets[lhs->state_offsets[i + 1]] -
+                       lhs->arc_offsets[lhs->state_offsets[i]]) + 1.0;
+  const FstError e = run_sharded(
+      call.devices, call.nsh, num, cost,
+      [&](Shard& S) { return run_lattice_lhs_shard(S, *b, *lhs, lattice_flags); }, out);
+  return call.close(e, "fst_compose_frozen_lhs_batch", out, fst_lattice_batch_free);
+}
+
+void fst_lattice_batch_free(FstLatticeBatch* r) {
+  if (!r) return;
+  pin_release(r->status);
+  pin_release(const_cast<uint64_t*>(r->fsts.state_offsets));
+  pin_release(const_cast<uint32_t*>(r->fsts.start));
+  pin_release(const_cast<double*>(r->fsts.final_weights));
+  pin_release(const_cast<uint64_t*>(r->fsts.arc_offsets));
+  pin_release(const_cast<uint32_t*>(r->fsts.ilabels));
+  pin_release(const_cast<uint32_t*>(r->fsts.olabels));
+  pin_release(const_cast<double*>(r->fsts.weights));
+  pin_release(const_cast<uint32_t*>(r->fsts.nextstates));
+  std::memset(r, 0, sizeof(*r));
+}
+
+// Chains in, lattices out, all on the device: the chain instances into an arena of the
+// library's own (grown from the cursors as the host entry's), then the compaction straight
+// into the caller's arrays when they hold the batch.
+FstError fst_device_compose_frozen(FstHandle b_handle, const uint32_t* d_labels,
+                                   const uint64_t* d_offsets, uint32_t num_strings,
+                                   uint32_t max_len, uint32_t lattice_flags,
+                                   const FstBatchOptions* opts, const FstDeviceLattices* o,
+                                   uint64_t needed[2], void* stream) {
+  if (!o || !needed || !d_offsets || !flags_ok(opts) || !lattice_flags_ok(lattice_flags))
+    return FST_INVALID_ARG;
+  if (!o->state_offsets || !o->arc_offsets || (num_strings && (!o->status || !o->start)))
+    return FST_INVALID_ARG;
+  if ((o->state_capacity && !o->final_weights) ||
+      (o->arc_capacity && (!o->ilabels || !o->olabels || !o->weights || !o->nextstates)))
+    return FST_INVALID_ARG;
+  std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
+  if (!b) return FST_INVALID_ARG;
+  if (!gpu_available()) return FST_INVALID_ARG;
+  DeviceRestore_ restore;
+  const int dev = opts && opts->device >= 0 ? opts->device : current_device();
+  if (dev < 0 || hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  DeviceFst* D = b->device(dev);
+  if (!D) return FST_OOM;
+  DeviceEngine::Lease E = DeviceEngine::acquire(dev);
+  if (!E) return FST_INVALID_ARG;
+  const hipStream_t s = E.use((hipStream_t)stream);
+  // the arena and the statuses are declared before the drain, so they are destroyed after
+  // it: every return waits for what the call queued (the gather reads the arena) before
+  // those blocks go back to the pool
+  std::unique_ptr<LatShard> lat;
+  std::unique_ptr<DevOut> keep;
+  StreamDrain drain{{s}};
+  needed[0] = needed[1] = 0;
+  ChainInput in{{d_labels}, d_offsets, num_strings, max_len};
+  uint64_t first = 0, last = 0;
+  if (num_strings && (!read_u64(&first, d_offsets, s) || !read_u64(&last, d_offsets + num_strings, s)))
+    return FST_OOM;
+  if (last < first) return FST_INVALID_ARG;
+  const uint64_t est = 8 * ((last - first) + num_strings) + 4ull * num_strings + 1024;
+  if (FstError e = run_lattice_arena(E, *D, in, nullptr, lattice_flags, est, 2 * est, &lat, &keep);
+      e != FST_OK)
+    return e;
+  LatticeCsrDev csr{};
+  csr.status = o->status;
+  csr.state_offsets = o->state_offsets;
+  csr.start = o->start;
+  csr.final_w = o->final_weights;
+  csr.arc_offsets = o->arc_offsets;
+  csr.il = o->ilabels;
+  csr.ol = o->olabels;
+  csr.w = o->weights;
+  csr.next = o->nextstates;
+  csr.state_cap = o->state_capacity;
+  csr.arc_cap = o->arc_capacity;
+  if (E->compact_lattices_count(keep->v.status, lat->arena, num_strings, csr, needed, s) !=
+      hipSuccess)
+    return FST_OOM;
+  if (needed[0] > lat->arena.state_cap || needed[1] > lat->arena.arc_cap) return FST_OOM;
+  // too small: the statuses and `needed` stand, nothing else is written
+  if (needed[0] > csr.state_cap || needed[1] > csr.arc_cap) return FST_OK;
+  if (E->compact_lattices(lat->arena, num_strings, csr, s) != hipSuccess) return FST_OOM;
+  return FST_OK;  // (the drain waits for the gather, then `keep` and `lat` go)
 }
 
 // The device-resident form: d_lhs's arrays are device memory, used in place.  The host reads

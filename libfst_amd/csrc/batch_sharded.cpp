@@ -1,7 +1,7 @@
 // batch_sharded.cpp -- host batches through the path arena: one engine run with arena
-// growth, the shards of a call and their result sinks (labels, text), the pipelined
-// one-device batch, and the per-shard compute steps (pipeline stages, text, general lhs, and
-// pipelines on a general first stage).
+// growth, the shards of a call and their result sinks (labels, text, lattices), the pipelined
+// one-device batch, and the per-shard compute steps (pipeline stages, text, general lhs,
+// pipelines on a general first stage, and the lattice batch with its own arena).
 #include <cmath>
 #include <condition_variable>
 
@@ -165,6 +165,90 @@ FstError shard_text_download(Shard& S, FstTextResult* out, uint64_t byte_base) {
     return FST_OOM;
   if (byte_base)
     for (uint32_t i = S.s0; i < S.s1; ++i) out->text_offsets[i] += byte_base;
+  return FST_OK;
+}
+
+// ---- Lattice results (fst_compose_frozen_batch) ----------------------------------------
+// The lattice sink's compaction: count and scan (the totals come back), the shard's arrays in
+// FstLhsBatch's layout sized from them, then the gather; the arena goes back to the pool.
+FstError shard_lattice_compact(Shard& S) {
+  if (!S.lat) return FST_OOM;
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  LatShard& Ls = *S.lat;
+  // a failure drains the stream before the shard's buffers go back to the pool
+  StreamDrain drain{{stream}};
+  Ls.status = std::make_unique<DevBuf>(num * 4ull);
+  Ls.soff = std::make_unique<DevBuf>((num + 1ull) * 8);
+  Ls.start = std::make_unique<DevBuf>(num * 4ull);
+  if (!Ls.status->p || !Ls.soff->p || !Ls.start->p) return FST_OOM;
+  LatticeCsrDev csr{};
+  csr.status = (int32_t*)Ls.status->p;
+  csr.state_offsets = (uint64_t*)Ls.soff->p;
+  csr.start = (uint32_t*)Ls.start->p;
+  uint64_t needed[2] = {0, 0};
+  if (S.E->compact_lattices_count(S.keep->v.status, Ls.arena, num, csr, needed, stream) !=
+      hipSuccess)
+    return FST_OOM;
+  // an engine bug: OK items own more than the arena holds
+  if (needed[0] > Ls.arena.state_cap || needed[1] > Ls.arena.arc_cap) return FST_OOM;
+  Ls.fin = std::make_unique<DevBuf>(needed[0] * 8);
+  Ls.aoffs = std::make_unique<DevBuf>((needed[0] + 1) * 8);
+  Ls.il = std::make_unique<DevBuf>(needed[1] * 4);
+  Ls.ol = std::make_unique<DevBuf>(needed[1] * 4);
+  Ls.next = std::make_unique<DevBuf>(needed[1] * 4);
+  Ls.w = std::make_unique<DevBuf>(needed[1] * 8);
+  if (!Ls.fin->p || !Ls.aoffs->p || !Ls.il->p || !Ls.ol->p || !Ls.next->p || !Ls.w->p)
+    return FST_OOM;
+  csr.final_w = (double*)Ls.fin->p;
+  csr.arc_offsets = (uint64_t*)Ls.aoffs->p;
+  csr.il = (uint32_t*)Ls.il->p;
+  csr.ol = (uint32_t*)Ls.ol->p;
+  csr.w = (double*)Ls.w->p;
+  csr.next = (uint32_t*)Ls.next->p;
+  csr.state_cap = needed[0];
+  csr.arc_cap = needed[1];
+  // (synchronised: the download may run on another engine's stream)
+  if (S.E->compact_lattices(Ls.arena, num, csr, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return FST_OOM;
+  drain.done = true;
+  Ls.item.reset();
+  Ls.afin.reset();
+  Ls.aaoff.reset();
+  Ls.ail.reset();
+  Ls.aol.reset();
+  Ls.aw.reset();
+  Ls.anext.reset();
+  S.tot = needed[0];
+  S.tot2 = needed[1];
+  return FST_OK;
+}
+
+// D2H of a compacted lattice shard at its item range, its first state and its first arc; the
+// two offset arrays are then moved by those bases (the closing entries: the sink's finish).
+FstError shard_lattice_download(Shard& S, FstLatticeBatch* out, uint64_t sbase, uint64_t abase) {
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  const LatShard& Ls = *S.lat;
+  const FstLhsBatch& F = out->fsts;
+  uint64_t* soff = const_cast<uint64_t*>(F.state_offsets);
+  uint64_t* aoff = const_cast<uint64_t*>(F.arc_offsets);
+  if (!(d2h(out->status + S.s0, Ls.status->p, num * 4ull, stream) &&
+        d2h(const_cast<uint32_t*>(F.start) + S.s0, Ls.start->p, num * 4ull, stream) &&
+        d2h(soff + S.s0, Ls.soff->p, num * 8ull, stream) &&
+        d2h(const_cast<double*>(F.final_weights) + sbase, Ls.fin->p, S.tot * 8, stream) &&
+        d2h(aoff + sbase, Ls.aoffs->p, S.tot * 8, stream) &&
+        d2h(const_cast<uint32_t*>(F.ilabels) + abase, Ls.il->p, S.tot2 * 4, stream) &&
+        d2h(const_cast<uint32_t*>(F.olabels) + abase, Ls.ol->p, S.tot2 * 4, stream) &&
+        d2h(const_cast<uint32_t*>(F.nextstates) + abase, Ls.next->p, S.tot2 * 4, stream) &&
+        d2h(const_cast<double*>(F.weights) + abase, Ls.w->p, S.tot2 * 8, stream)) ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return FST_OOM;
+  if (sbase)
+    for (uint32_t i = S.s0; i < S.s1; ++i) soff[i] += sbase;
+  if (abase)
+    for (uint64_t s = sbase; s < sbase + S.tot; ++s) aoff[s] += abase;
   return FST_OK;
 }
 
@@ -342,13 +426,13 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
     // (two sharded calls on one device cannot deadlock)
     S.E = DeviceEngine::Lease();
   };
-  auto phase2 = [&](Shard& S, uint64_t base) {
+  auto phase2 = [&](Shard& S, uint64_t base, uint64_t base2) {
     if (hipSetDevice(S.dev) != hipSuccess) {
       S.err = FST_OOM;
       return;
     }
     S.E = DeviceEngine::acquire(S.dev);
-    S.err = S.E ? sink.download(S, base) : FST_OOM;
+    S.err = S.E ? sink.download(S, base, base2) : FST_OOM;
     S.E = DeviceEngine::Lease();
   };
   auto each = [&](const std::function<void(uint32_t)>& f) {
@@ -359,17 +443,21 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
     for (auto& x : th) x.join();
   };
   each([&](uint32_t j) { phase1(sh[j]); });
-  uint64_t tot = 0;
+  uint64_t tot = 0, tot2 = 0;
   for (Shard& S : sh) {
     if (S.err != FST_OK) return S.err;
     tot += S.tot;
+    tot2 += S.tot2;
   }
   if (t_prof) t_prof->lap(4);
-  if (!sink.alloc(tot)) return FST_OOM;
-  std::vector<uint64_t> base(nsh, 0);
-  for (uint32_t j = 1; j < nsh; ++j) base[j] = base[j - 1] + sh[j - 1].tot;
-  each([&](uint32_t j) { phase2(sh[j], base[j]); });
-  sink.finish(tot);
+  if (!sink.alloc(tot, tot2)) return FST_OOM;
+  std::vector<uint64_t> base(nsh, 0), base2(nsh, 0);
+  for (uint32_t j = 1; j < nsh; ++j) {
+    base[j] = base[j - 1] + sh[j - 1].tot;
+    base2[j] = base2[j - 1] + sh[j - 1].tot2;
+  }
+  each([&](uint32_t j) { phase2(sh[j], base[j], base2[j]); });
+  sink.finish(tot, tot2);
   LaunchStats agg = sh[0].stats;  // the slowest shard's kernel time, launches summed
   for (uint32_t j = 1; j < nsh; ++j) {
     agg.kernel_ms = std::max(agg.kernel_ms, sh[j].stats.kernel_ms);
@@ -386,9 +474,28 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
                      const std::vector<double>& cost, const ShardCompute& compute,
                      FstBatchResult* out) {
   const ShardSink sink{shard_compact,
-                       [=](uint64_t tot) { return alloc_result(out, num, tot); },
-                       [=](Shard& S, uint64_t base) { return shard_download(S, out, base); },
-                       [=](uint64_t tot) { out->path_offsets[num] = tot; }};
+                       [=](uint64_t tot, uint64_t) { return alloc_result(out, num, tot); },
+                       [=](Shard& S, uint64_t base, uint64_t) {
+                         return shard_download(S, out, base);
+                       },
+                       [=](uint64_t tot, uint64_t) { out->path_offsets[num] = tot; }};
+  return run_sharded(devices, nsh, num, cost, compute, sink);
+}
+
+FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
+                     const std::vector<double>& cost, const ShardCompute& compute,
+                     FstLatticeBatch* out) {
+  const ShardSink sink{shard_lattice_compact,
+                       [=](uint64_t states, uint64_t arcs) {
+                         return alloc_lattice_result(out, num, states, arcs);
+                       },
+                       [=](Shard& S, uint64_t sbase, uint64_t abase) {
+                         return shard_lattice_download(S, out, sbase, abase);
+                       },
+                       [=](uint64_t states, uint64_t arcs) {
+                         const_cast<uint64_t*>(out->fsts.state_offsets)[num] = states;
+                         const_cast<uint64_t*>(out->fsts.arc_offsets)[states] = arcs;
+                       }};
   return run_sharded(devices, nsh, num, cost, compute, sink);
 }
 
@@ -396,9 +503,11 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
                      const std::vector<double>& cost, const ShardCompute& compute,
                      FstTextResult* out) {
   const ShardSink sink{shard_text,
-                       [=](uint64_t tot) { return alloc_text_result(out, num, tot); },
-                       [=](Shard& S, uint64_t base) { return shard_text_download(S, out, base); },
-                       [=](uint64_t tot) { out->text_offsets[num] = tot; }};
+                       [=](uint64_t tot, uint64_t) { return alloc_text_result(out, num, tot); },
+                       [=](Shard& S, uint64_t base, uint64_t) {
+                         return shard_text_download(S, out, base);
+                       },
+                       [=](uint64_t tot, uint64_t) { out->text_offsets[num] = tot; }};
   return run_sharded(devices, nsh, num, cost, compute, sink);
 }
 
@@ -592,16 +701,26 @@ FstError run_text_shard(Shard& S, const Stages& fs, const uint8_t* text, const u
   return e;
 }
 
-// One shard (items [i0, i1) of the caller's batch) on the shard's engine: the items staged
-// into one pinned block -- descriptors, per-state arc offsets local to the item, finals, the
-// four arc arrays, the two eager item lists -- and uploaded with one DMA; then the engine
-// (DeviceEngine::run_lhs_batch), its arena grown on OUTPUT_FULL as run_chain_batch_dev's is.
-FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n, int semantics) {
-  const int dev = S.E->dev();
-  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
-  DeviceFst* D = b.device(dev);
-  if (!D) return FST_OOM;
-  const hipStream_t stream = S.E.stream();
+// The items of one shard (items [i0, i1) of the caller's batch) staged into one pinned block --
+// descriptors, per-state arc offsets local to the item, finals, the four arc arrays, the two
+// eager item lists -- and uploaded with one DMA.  The 1-best shard (run_lhs_shard) and the
+// lattice shard (run_lattice_lhs_shard) share it.
+namespace {
+struct LhsStaged {
+  std::unique_ptr<DevBuf> blk;
+  PinnedVec<uint8_t> hin;
+  ChainInput in{};
+  GraphInput g{};
+  const uint32_t* items_nonneg = nullptr;
+  const uint32_t* items_replay = nullptr;
+  uint32_t num_nonneg = 0, num_replay = 0;
+  uint64_t num_states = 0, num_arcs = 0;
+};
+
+// Queues the upload on `stream`; the caller drains the stream before *st goes (the upload or
+// a kernel may still be using its two blocks).
+FstError stage_lhs_items(Shard& S, DeviceFst* D, const FstLhsBatch& L, hipStream_t stream,
+                         LhsStaged* st) {
   const uint32_t i0 = S.s0, num = S.s1 - S.s0;
   const uint64_t sb = L.state_offsets[i0], ns = L.state_offsets[S.s1] - sb;
   const uint64_t ab = L.arc_offsets[sb], na = L.arc_offsets[L.state_offsets[S.s1]] - ab;
@@ -610,12 +729,11 @@ FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n,
                  o_w = o_fin + al(ns * 8), o_il = o_w + al(na * 8), o_ol = o_il + al(na * 4),
                  o_nx = o_ol + al(na * 4), o_la = o_nx + al(na * 4), o_lb = o_la + al(num * 4ull),
                  end = o_lb + al(num * 4ull);
-  DevBuf blk(end);
-  PinnedVec<uint8_t> hin(end);
+  st->blk = std::make_unique<DevBuf>(end);
+  st->hin.resize(end);
+  DevBuf& blk = *st->blk;
+  PinnedVec<uint8_t>& hin = st->hin;
   if (!blk.p) return FST_OOM;
-  // every return drains the stream before `blk` and `hin` go back to their pools: the
-  // upload or a kernel (the engine can fail after launching some) may still be using them
-  StreamDrain drain{{stream}};
   LhsDesc* desc = (LhsDesc*)(hin.data() + o_desc);
   uint32_t* soff = (uint32_t*)(hin.data() + o_soff);
   uint32_t* la = (uint32_t*)(hin.data() + o_la);
@@ -663,10 +781,10 @@ FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n,
   if (hipMemcpyAsync(blk.p, hin.data(), end, hipMemcpyHostToDevice, stream) != hipSuccess)
     return FST_OOM;
   uint8_t* p = (uint8_t*)blk.p;
-  ChainInput in{};
+  ChainInput& in = st->in;
   in.lhs_desc = (const LhsDesc*)(p + o_desc);
   in.num_strings = num;
-  GraphInput g{};
+  GraphInput& g = st->g;
   g.state_off = (const uint32_t*)(p + o_soff);
   g.final_w = (const double*)(p + o_fin);
   g.arc_w = (const double*)(p + o_w);
@@ -675,16 +793,181 @@ FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n,
   g.arc_next = (const uint32_t*)(p + o_nx);
   g.start = kNoState;
   g.max_outdeg = max_outdeg;
+  st->items_nonneg = (const uint32_t*)(p + o_la);
+  st->items_replay = (const uint32_t*)(p + o_lb);
+  st->num_nonneg = n_a;
+  st->num_replay = n_b;
+  st->num_states = ns;
+  st->num_arcs = na;
   if (t_prof) t_prof->lap(0);
+  return FST_OK;
+}
+}  // namespace
+
+// One shard of general lhs on the shard's engine: the staged items through
+// DeviceEngine::run_lhs_batch, its arena grown on OUTPUT_FULL as run_chain_batch_dev's is.
+FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n, int semantics) {
+  const int dev = S.E->dev();
+  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  DeviceFst* D = b.device(dev);
+  if (!D) return FST_OOM;
+  const hipStream_t stream = S.E.stream();
+  LhsStaged st;
+  // every return drains the stream before the staged blocks go back to their pools: the
+  // upload or a kernel (the engine can fail after launching some) may still be using them
+  StreamDrain drain{{stream}};
+  if (FstError e = stage_lhs_items(S, D, L, stream, &st); e != FST_OK) return e;
   HostPaths h;  // (the statuses)
   return run_arena(
-      stream, num, std::max<uint64_t>(4 * na + 16, 1024), "lhs batch engine failed", false,
-      [&](const BatchOutDev& v, LaunchStats* st) {
+      stream, S.s1 - S.s0, std::max<uint64_t>(4 * st.num_arcs + 16, 1024),
+      "lhs batch engine failed", false,
+      [&](const BatchOutDev& v, LaunchStats* ls) {
         LhsRoute route;
-        return S.E->run_lhs_batch(*D, in, g, n, semantics, (const uint32_t*)(p + o_la), n_a,
-                                  (const uint32_t*)(p + o_lb), n_b, v, stream, st, &route);
+        return S.E->run_lhs_batch(*D, st.in, st.g, n, semantics, st.items_nonneg, st.num_nonneg,
+                                  st.items_replay, st.num_replay, v, stream, ls, &route);
       },
       &h, &S.keep);
+}
+
+// ---- Lattice shards ---------------------------------------------------------------------
+
+bool alloc_lattice_result(FstLatticeBatch* out, uint32_t num, uint64_t states, uint64_t arcs) {
+  FstLhsBatch& F = out->fsts;
+  F.num_fsts = num;
+  out->total_states = states;
+  out->total_arcs = arcs;
+  out->status = (int32_t*)pin_alloc(std::max<size_t>(num, 1) * 4);
+  F.state_offsets = (uint64_t*)pin_alloc((num + 1ull) * 8);
+  F.start = (uint32_t*)pin_alloc(std::max<size_t>(num, 1) * 4);
+  F.final_weights = (double*)pin_alloc(std::max<uint64_t>(states, 1) * 8);
+  F.arc_offsets = (uint64_t*)pin_alloc((states + 1) * 8);
+  F.ilabels = (uint32_t*)pin_alloc(std::max<uint64_t>(arcs, 1) * 4);
+  F.olabels = (uint32_t*)pin_alloc(std::max<uint64_t>(arcs, 1) * 4);
+  F.nextstates = (uint32_t*)pin_alloc(std::max<uint64_t>(arcs, 1) * 4);
+  F.weights = (double*)pin_alloc(std::max<uint64_t>(arcs, 1) * 8);
+  return out->status && F.state_offsets && F.start && F.final_weights && F.arc_offsets &&
+         F.ilabels && F.olabels && F.nextstates && F.weights;
+}
+
+FstError run_lattice_arena(DeviceEngine::Lease& E, DeviceFst& D, const ChainInput& in,
+                           const GraphInput* lhs, uint32_t lattice_flags, uint64_t est_states,
+                           uint64_t est_arcs, std::unique_ptr<LatShard>* lat,
+                           std::unique_ptr<DevOut>* keep) {
+  const hipStream_t stream = E.stream();
+  const uint32_t num = in.num_strings;
+  uint64_t cap[2] = {est_states, est_arcs};
+  if (const char* e = std::getenv("FSTAMD_LATTICE_ARENA"))  // tests: the arena's first size
+    if (*e) {
+      char* end = nullptr;
+      cap[0] = std::strtoull(e, &end, 10);
+      cap[1] = end && *end == ',' ? std::strtoull(end + 1, nullptr, 10) : cap[0];
+    }
+  constexpr int kAttempts = 4;
+  for (int attempt = 0; attempt < kAttempts; ++attempt) {
+    for (uint64_t& c : cap) c = (std::max<uint64_t>(c, 4) + 3) & ~3ull;
+    auto L = std::make_unique<LatShard>();
+    auto out = std::make_unique<DevOut>(num, 1);  // statuses; no path is written
+    L->item = std::make_unique<DevBuf>(num * sizeof(LatItem));
+    L->afin = std::make_unique<DevBuf>(cap[0] * 8);
+    L->aaoff = std::make_unique<DevBuf>(cap[0] * 4);
+    L->ail = std::make_unique<DevBuf>(cap[1] * 4);
+    L->aol = std::make_unique<DevBuf>(cap[1] * 4);
+    L->anext = std::make_unique<DevBuf>(cap[1] * 4);
+    L->aw = std::make_unique<DevBuf>(cap[1] * 8);
+    L->cursor = std::make_unique<DevBuf>(16);
+    if (!out->ok() || !L->item->p || !L->afin->p || !L->aaoff->p || !L->ail->p || !L->aol->p ||
+        !L->anext->p || !L->aw->p || !L->cursor->p)
+      return FST_OOM;
+    LatticeOutDev& a = L->arena;
+    a.item = (LatItem*)L->item->p;
+    a.fin = (double*)L->afin->p;
+    a.aoff = (uint32_t*)L->aaoff->p;
+    a.il = (uint32_t*)L->ail->p;
+    a.ol = (uint32_t*)L->aol->p;
+    a.next = (uint32_t*)L->anext->p;
+    a.w = (double*)L->aw->p;
+    a.state_cap = cap[0];
+    a.arc_cap = cap[1];
+    a.cursor = (unsigned long long*)L->cursor->p;
+    a.project = (lattice_flags & FST_LATTICE_PROJECT_OUTPUT) ? 1u : 0u;
+    PinnedVec<int32_t> status(num);
+    unsigned long long need[2] = {0, 0};
+    // a failure drains the stream before the arena and the read-back targets above go
+    StreamDrain drain{{stream}};
+    LaunchStats st;
+    LhsRoute route;
+    hipError_t err = E->run_lattice_batch(D, in, lhs, a, out->v, stream, &st, &route);
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);
+    if (t_prof) {
+      t_prof->lap(2);
+      ++t_prof->runs;
+    }
+    if (err != hipSuccess) {
+      std::fprintf(stderr, "[libfst_amd] lattice batch engine failed: %s\n",
+                   hipGetErrorString(err));
+      return FST_OOM;
+    }
+    t_last_stats = st;
+    if (!d2h(status.data(), out->v.status, num * 4ull, stream) ||
+        !d2h(need, a.cursor, sizeof(need), stream) || hipStreamSynchronize(stream) != hipSuccess)
+      return FST_OOM;
+    drain.done = true;
+    bool full = false;
+    for (uint32_t i = 0; i < num; ++i) full |= status[i] == kPathOutputFull;
+    // the last attempt's result stands: items still OUTPUT_FULL keep that status
+    if (!full || attempt + 1 == kAttempts) {
+      *lat = std::move(L);
+      *keep = std::move(out);
+      return FST_OK;
+    }
+    // every item reserves with atomicAdd before it checks the capacities, so the cursors end
+    // at what the items that reached the emission need: one rerun suffices
+    cap[0] = std::max<uint64_t>(cap[0], need[0]);
+    cap[1] = std::max<uint64_t>(cap[1], need[1]);
+  }
+  return FST_OOM;  // unreachable: the last attempt returns above
+}
+
+FstError run_lattice_chain_shard(Shard& S, FrozenFst& b, const uint32_t* labels,
+                                 const uint64_t* offsets, uint32_t lattice_flags) {
+  const int dev = S.E->dev();
+  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  DeviceFst* D = b.device(dev);
+  if (!D) return FST_OOM;
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  std::vector<uint64_t> rebased;
+  const uint32_t max_len = rebase_offsets(offsets, num, &rebased);
+  const uint64_t total = rebased[num];
+  DevBuf lab(total * 4), off((num + 1ull) * 8);
+  if (!lab.p || !off.p) return FST_OOM;
+  // every return drains the stream before the inputs go back to the pool
+  StreamDrain drain{{stream}};
+  if (total && hipMemcpyAsync(lab.p, labels + offsets[0], total * 4, hipMemcpyHostToDevice,
+                              stream) != hipSuccess)
+    return FST_OOM;
+  if (hipMemcpyAsync(off.p, rebased.data(), (num + 1ull) * 8, hipMemcpyHostToDevice, stream) !=
+      hipSuccess)
+    return FST_OOM;
+  if (t_prof) t_prof->lap(0);
+  ChainInput in{{(const uint32_t*)lab.p}, (const uint64_t*)off.p, num, max_len};
+  // a guess (8 tuples per label, 2 arcs per tuple); the cursors correct it in one rerun
+  const uint64_t est = 8 * (total + num) + 4ull * num + 1024;
+  return run_lattice_arena(S.E, *D, in, nullptr, lattice_flags, est, 2 * est, &S.lat, &S.keep);
+}
+
+FstError run_lattice_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L,
+                               uint32_t lattice_flags) {
+  const int dev = S.E->dev();
+  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  DeviceFst* D = b.device(dev);
+  if (!D) return FST_OOM;
+  const hipStream_t stream = S.E.stream();
+  LhsStaged st;
+  StreamDrain drain{{stream}};  // (as run_lhs_shard)
+  if (FstError e = stage_lhs_items(S, D, L, stream, &st); e != FST_OK) return e;
+  const uint64_t est = 8 * (st.num_states + st.num_arcs + (S.s1 - S.s0)) + 1024;
+  return run_lattice_arena(S.E, *D, st.in, &st.g, lattice_flags, est, 2 * est, &S.lat, &S.keep);
 }
 
 // One shard of a pipeline on a general first stage: stage 1 is run_lhs_shard as it stands,

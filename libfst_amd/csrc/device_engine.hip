@@ -412,6 +412,10 @@ enum Scratch : size_t {
   kLhsPrepNonneg,
   kLhsPrepReplay,
   kLhsPrepTotals,
+  kLatDesc,
+  kLatCntStates,
+  kLatCntArcs,
+  kLatArcBase,
   kNumScratch
 };
 
@@ -2717,8 +2721,30 @@ hipError_t DeviceEngine::run_lhs_eager(const DeviceFst& rhs, const ChainInput& i
   HIP_TRY(hipMemsetAsync(cnt, 0, 32, stream));
   HIP_TRY(hipMemcpyAsync(cnt, &count, 4, hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(list, items, (size_t)count * 4, hipMemcpyDeviceToDevice, stream));
+  BfsLadder L;
+  L.tiny = !replay;
+  L.replay = replay;
+  L.lattice_only = 0;
+  L.per_cu = [](int kind) { return lhs_eager_per_cu(kind); };
+  L.launch = [&](int kind, const BfsWs& ws, unsigned int* next_item, const uint32_t* cur,
+                 const uint32_t* cur_count, uint32_t grid) {
+    return launch_lhs_eager(kind, rhs.view, in, lhs, n, next_item, cur, cur_count, ws, out, grid,
+                            stream);
+  };
+  return run_bfs_ladder(count, list, list2, cnt, out.status, L, stream, route, grid_out);
+}
+
+// The ladder itself, shared by run_lhs_eager and run_lattice_batch: `list` holds `count`
+// items and cnt[0] = count on the device; cnt[1] is the item counter, cnt[2] the next list's
+// count.  L.launch queues one tier's kernel; L.per_cu gives an LDS tier's resident workgroups
+// per CU.  FSTAMD_BFS_TINY=0 turns the LDS tiers off, FSTAMD_GRAPH_GRID caps the grid.
+hipError_t DeviceEngine::run_bfs_ladder(uint32_t count, uint32_t* list, uint32_t* list2,
+                                        uint32_t* cnt, const int32_t* status,
+                                        const BfsLadder& L, hipStream_t stream, LhsRoute* route,
+                                        uint32_t* grid_out) {
   const char* te = std::getenv("FSTAMD_BFS_TINY");
-  const bool tiny = !replay && !(te && std::strcmp(te, "0") == 0);
+  const bool tiny = L.tiny && !(te && std::strcmp(te, "0") == 0);
+  const bool replay = L.replay;
   const uint32_t cap = grid_cap("FSTAMD_GRAPH_GRID");
   for (int tier = tiny ? -2 : 0; count > 0; ++tier) {
     const TinyCaps tc = tiny_caps(tier == -2 ? 1 : 2);
@@ -2729,7 +2755,7 @@ hipError_t DeviceEngine::run_lhs_eager(const DeviceFst& rhs, const ChainInput& i
                      : tier == -1 ? kLhsTierTiny256
                      : tier == 0 ? kLhsTierWave
                                  : kLhsTierWG;
-    const uint64_t per_cu = tier < 0 ? (uint64_t)lhs_eager_per_cu(kind)
+    const uint64_t per_cu = tier < 0 ? (uint64_t)L.per_cu(kind)
                             : tier == 0 ? 4 * FSTAMD_BFS_WAVES64
                                         : 1;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(
@@ -2744,7 +2770,7 @@ hipError_t DeviceEngine::run_lhs_eager(const DeviceFst& rhs, const ChainInput& i
     ws.hcap = c.hcap;
     ws.lcap = c.lcap;
     ws.wd_ticks = watchdog_ticks();
-    ws.lattice_only = 0;
+    ws.lattice_only = L.lattice_only;
     ws.lazy = 0;
     ws.prof = nullptr;
     if (replay) {  // heap + settled flags per workgroup (kernels/eager_bfs.hpp)
@@ -2753,12 +2779,11 @@ hipError_t DeviceEngine::run_lhs_eager(const DeviceFst& rhs, const ChainInput& i
       if (!ws.replay) return hipErrorOutOfMemory;
     }
     HIP_TRY(hipMemsetAsync(cnt + 1, 0, 8, stream));  // item counter + next list count
-    HIP_TRY(launch_lhs_eager(kind, rhs.view, in, lhs, n, cnt + 1, list, cnt, ws, out, grid,
-                             stream));
+    HIP_TRY(L.launch(kind, ws, cnt + 1, list, cnt, grid));
     route->t[std::min(tier + 2, 3)] += count;
     route->tiers_run += 1;
     if (grid_out) *grid_out = std::max(*grid_out, grid);
-    collect_list_kernel<<<(count + 255) / 256, 256, 0, stream>>>(list, cnt, out.status,
+    collect_list_kernel<<<(count + 255) / 256, 256, 0, stream>>>(list, cnt, status,
                                                                  kPathOverflow, list2, cnt + 2);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&count, cnt + 2, 4, hipMemcpyDeviceToHost, stream));
@@ -2854,6 +2879,111 @@ hipError_t DeviceEngine::run_lhs_batch(const DeviceFst& rhs, const ChainInput& i
   }
   if (route) *route = r;
   return hipSuccess;
+}
+
+// ---- lattice batch (lattice_batch.hip holds the kernel instances) ----------------------
+
+// run_lhs_eager's ladder with the emitting instances, over one list of every item: compose
+// never orders weights, so there is no replay route.
+hipError_t DeviceEngine::run_lattice_batch(const DeviceFst& rhs, const ChainInput& in,
+                                           const GraphInput* lhs, const LatticeOutDev& lat,
+                                           const BatchOutDev& out_in, hipStream_t stream,
+                                           LaunchStats* stats, LhsRoute* route) {
+  HIP_TRY(hipSetDevice(dev_));
+  const uint32_t num = in.num_strings;
+  const bool chain = lhs == nullptr;
+  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);  // [8..11], as run_bfs_chain
+  uint32_t* list = (uint32_t*)scratch(kBfsList, (size_t)num * 4);
+  uint32_t* list2 = (uint32_t*)scratch(kBfsList2, (size_t)num * 4);
+  LatticeOutDev* d_lat = (LatticeOutDev*)scratch(kLatDesc, sizeof(LatticeOutDev));
+  if (!ctr || !list || !list2 || !d_lat) return hipErrorOutOfMemory;
+  HIP_TRY(hipMemsetAsync(ctr, 0, 64, stream));
+  HIP_TRY(hipMemsetAsync(lat.cursor, 0, 2 * sizeof(unsigned long long), stream));
+  LhsRoute r;
+  uint32_t grid_max = 0;
+  if (stats) {
+    stats->engine = 10;
+    stats->grid = 0;
+    stats->launches = 0;
+  }
+  if (num == 0) return hipSuccess;
+  if ((lat.state_cap | lat.arc_cap) & 3u) return hipErrorInvalidValue;
+  HIP_TRY(hipMemcpyAsync(d_lat, &lat, sizeof(lat), hipMemcpyHostToDevice, stream));
+  BatchOutDev out = out_in;
+  out.slots = nullptr;
+  out.host_ol = nullptr;
+  out.first_status = nullptr;
+  out.lattice = d_lat;
+  // every item starts as INTERNAL: an item no kernel finished can never read as a result.  A
+  // NaN in the rhs: every item is UNSUPPORTED and none is run (for a general lhs its
+  // descriptor says so too)
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out.status, rhs.nan ? kPathUnsupported : kPathInternal,
+                            num, stream));
+  if (stats) HIP_TRY(hipEventRecord(ev0_, stream));
+  uint32_t* cnt = ctr + 8;
+  uint32_t count = rhs.nan ? 0u : num;
+  if (count) {
+    collect_status2_kernel<<<(num + 255) / 256, 256, 0, stream>>>(out.status, num, kPathInternal,
+                                                                  kPathInternal, list, cnt);
+    HIP_TRY(hipGetLastError());
+  }
+  const GraphInput none{};
+  BfsLadder L;
+  L.tiny = true;
+  L.replay = false;
+  L.lattice_only = 1;
+  L.per_cu = [chain](int kind) { return lattice_per_cu(kind, chain); };
+  L.launch = [&](int kind, const BfsWs& ws, unsigned int* next_item, const uint32_t* cur,
+                 const uint32_t* cur_count, uint32_t grid) {
+    return launch_lattice(kind, chain, rhs.view, in, chain ? none : *lhs, next_item, cur,
+                          cur_count, ws, out, grid, stream);
+  };
+  HIP_TRY(run_bfs_ladder(count, list, list2, cnt, out.status, L, stream, &r, &grid_max));
+  if (stats) {
+    stats->grid = grid_max;
+    stats->launches = 2 * r.tiers_run;  // each tier: its kernel and the hand-over list
+    HIP_TRY(hipEventRecord(ev1_, stream));
+    HIP_TRY(finish_stats(ev0_, ev1_, stats));
+  }
+  if (std::getenv("FSTAMD_ROUTE_LOG"))
+    std::fprintf(stderr,
+                 "[libfst_amd route] lattice batch: items %u | tiny128 %u tiny256 %u tier0 %u "
+                 "tier1+ %u\n",
+                 num, r.t[0], r.t[1], r.t[2], r.t[3]);
+  if (route) *route = r;
+  return hipSuccess;
+}
+
+hipError_t DeviceEngine::compact_lattices_count(const int32_t* status, const LatticeOutDev& lat,
+                                                uint32_t num, const LatticeCsrDev& csr,
+                                                uint64_t needed[2], hipStream_t stream) {
+  HIP_TRY(hipSetDevice(dev_));
+  const size_t cb = ((size_t)num + 1) * 8 + 16;
+  uint64_t* cnt_s = (uint64_t*)scratch(kLatCntStates, cb);
+  uint64_t* cnt_a = (uint64_t*)scratch(kLatCntArcs, cb);
+  uint64_t* arc_base = (uint64_t*)scratch(kLatArcBase, cb);
+  if (!cnt_s || !cnt_a || !arc_base) return hipErrorOutOfMemory;
+  HIP_TRY(launch_lattice_count(status, lat.item, num, csr.status, cnt_s, cnt_a, stream));
+  size_t tbytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tbytes, cnt_s, csr.state_offsets, num + 1,
+                                           stream));
+  void* temp = scratch(kProjTemp, tbytes + 16);
+  if (!temp) return hipErrorOutOfMemory;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(temp, tbytes, cnt_s, csr.state_offsets, num + 1,
+                                           stream));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(temp, tbytes, cnt_a, arc_base, num + 1, stream));
+  HIP_TRY(hipMemcpyAsync(&needed[0], csr.state_offsets + num, 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(&needed[1], arc_base + num, 8, hipMemcpyDeviceToHost, stream));
+  return hipStreamSynchronize(stream);
+}
+
+hipError_t DeviceEngine::compact_lattices(const LatticeOutDev& lat, uint32_t num,
+                                          const LatticeCsrDev& csr, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(dev_));
+  const uint64_t* arc_base = (const uint64_t*)scratch(kLatArcBase, ((size_t)num + 1) * 8 + 16);
+  if (!arc_base) return hipErrorOutOfMemory;
+  const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(num, (uint32_t)num_cus_ * 32));
+  return launch_lattice_gather(lat, arc_base, csr, num, grid, stream);
 }
 
 hipError_t DeviceEngine::prepare_lhs(const DeviceFst& rhs, LhsPrepIn in, hipStream_t stream,

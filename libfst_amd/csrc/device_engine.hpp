@@ -15,6 +15,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -219,6 +220,10 @@ struct BatchOutDev {
   union {
     double* host_w = nullptr;
     const struct TextOutDev* text;
+    // the lattice batch (fst_compose_frozen_batch; the emitting instances of eager_bfs_kernel,
+    // lattice_batch.hip): where every item's lattice goes.  A third tenant of the same place:
+    // the emitting instances write no path, so neither of the other two is theirs
+    const struct LatticeOutDev* lattice;
   };
   // (host side, not read by kernels) when set, run_chain copies the statuses right after
   // the first tier here: which strings the pull tier finished (and copied out) itself
@@ -240,6 +245,44 @@ struct TextOutDev {
                        // olabel > 256 (the host reports UNSUPPORTED; the device status stays
                        // OK: the later tiers take every UNSUPPORTED string for theirs)
   double* total_w;     // [num] device: the serial fold of the path's weights and the final
+};
+
+// Lattice outputs of the lattice batch.  An item that finished its compose
+// reserves round4(N) states and round4(A) arcs in the arena with one atomicAdd on each cursor
+// (so every item starts 16-B aligned in every array and the copies are whole 16-B stores),
+// copies nfin / aoff (local offsets, N of them: the closing one is A) and the four arc arrays
+// there, and records where.  The cursors keep counting past the capacities: such an item
+// reports OUTPUT_FULL and the cursors end at what the batch needs.
+struct LatItem {
+  uint64_t spos, apos;  // first state / arc of the item in the arena
+  uint32_t n, a;        // its states and arcs
+  uint32_t pad[2];
+};
+static_assert(sizeof(LatItem) == 32, "two 16-B stores per item");
+struct LatticeOutDev {
+  LatItem* item;        // [num], defined for OK items
+  double* fin;          // [state_cap]
+  uint32_t* aoff;       // [state_cap] arc offsets local to the item
+  uint32_t* il;         // [arc_cap]
+  uint32_t* ol;
+  double* w;
+  uint32_t* next;
+  uint64_t state_cap, arc_cap;  // multiples of 4
+  unsigned long long* cursor;   // [2] states, arcs
+  uint32_t project;             // 1: il := ol (FST_LATTICE_PROJECT_OUTPUT)
+};
+// The compacted batch, in FstLhsBatch's layout (device memory).
+struct LatticeCsrDev {
+  int32_t* status;          // [num]
+  uint64_t* state_offsets;  // [num + 1]
+  uint32_t* start;          // [num]
+  double* final_w;          // [state_cap]
+  uint64_t* arc_offsets;    // [state_cap + 1]
+  uint32_t* il;             // [arc_cap]
+  uint32_t* ol;
+  double* w;
+  uint32_t* next;
+  uint64_t state_cap, arc_cap;
 };
 
 // Chain inputs (batch API) or one general lhs FST (single-call C ABI).
@@ -395,6 +438,19 @@ hipError_t launch_lhs_lazy(const RhsView& rhs, const ChainInput& in, const Graph
                            uint32_t n_best, unsigned int* next_item, const uint32_t* items,
                            uint32_t num_items, const LazyWs& ws, const BatchOutDev& out,
                            uint32_t grid, hipStream_t stream);
+// ---- lattice batch (lattice_batch.hip: the emitting instances of eager_bfs_kernel, chain and
+// kLhsBatch at the four LhsTier shapes, and the compaction kernels) ----
+int lattice_per_cu(int tier, bool chain);
+hipError_t launch_lattice(int tier, bool chain, const RhsView& rhs, const ChainInput& in,
+                          const GraphInput& lhs, unsigned int* next_item, const uint32_t* items,
+                          const uint32_t* num_items_dev, const BfsWs& ws, const BatchOutDev& out,
+                          uint32_t grid, hipStream_t stream);
+hipError_t launch_lattice_count(const int32_t* status, const LatItem* item, uint32_t num,
+                                int32_t* status_out, uint64_t* cnt_states, uint64_t* cnt_arcs,
+                                hipStream_t stream);
+hipError_t launch_lattice_gather(const LatticeOutDev& arena, const uint64_t* arc_base,
+                                 const LatticeCsrDev& csr, uint32_t num, uint32_t grid,
+                                 hipStream_t stream);
 // On-device preparation of a device-resident batch (kernels/lhs_prepare.hpp; lhs_batch.hip
 // holds the instances).  In: the caller's arrays in FstLhsBatch's layout, all device memory,
 // and their two extents as the host read them.  Out: descriptors, local arc offsets
@@ -549,6 +605,24 @@ class DeviceEngine {
   // `stream` (synchronised: the lattice is downloaded).
   hipError_t compose_lattice(const DeviceFst& rhs, const GraphInput& lhs, HostLattice* lat,
                              LaunchStats* stats, hipStream_t stream);
+  // The lattice batch (fst_compose_frozen_batch / _lhs_batch): the tier ladder of run_lhs_eager
+  // over every item, with the emitting instances of eager_bfs_kernel (chain: `lhs` null,
+  // in.labels / offsets; else in.lhs_desc and *lhs as for run_lhs_batch).  `lat` is the host
+  // copy of the arena's description; `out` carries statuses (its path arrays only take the
+  // zeroes of non-OK items).  Resets the arena's cursors.  Items no tier holds end OVERFLOW,
+  // items the arena cannot hold OUTPUT_FULL.  Synchronises `stream` between tiers.
+  hipError_t run_lattice_batch(const DeviceFst& rhs, const ChainInput& in, const GraphInput* lhs,
+                               const LatticeOutDev& lat, const BatchOutDev& out,
+                               hipStream_t stream, LaunchStats* stats, LhsRoute* route);
+  // The arena in item order, step 1: csr.status (non-OK items own nothing), csr.state_offsets
+  // and the items' arc bases (a workspace) by two scans.  Synchronises; needed = {states, arcs}.
+  hipError_t compact_lattices_count(const int32_t* status, const LatticeOutDev& lat, uint32_t num,
+                                    const LatticeCsrDev& csr, uint64_t needed[2],
+                                    hipStream_t stream);
+  // Step 2 (after step 1 on the same engine; needed within csr's capacities): start, finals,
+  // global arc offsets with the closing entry, and the arcs.  Asynchronous on `stream`.
+  hipError_t compact_lattices(const LatticeOutDev& lat, uint32_t num, const LatticeCsrDev& csr,
+                              hipStream_t stream);
   // Output tape of each path of a finished stage as the next stage's chain inputs
   // (printOutputString + compileString on device): next_labels = the path's non-epsilon
   // olabels.  A string whose status is not OK, or whose output has a label > 256, gets
@@ -650,6 +724,21 @@ class DeviceEngine {
                            uint32_t n, const uint32_t* items, uint32_t count, bool replay,
                            const BatchOutDev& out, hipStream_t stream, LhsRoute* route,
                            uint32_t* grid_out);
+  // The tier ladder of the general BFS engine over a device item list (LDS 128, LDS 256, tier
+  // 0 with one wave per item, then 256-thread tiers x8; OVERFLOW items move on), shared by
+  // run_lhs_eager and run_lattice_batch, which differ in the kernel a tier launches.
+  struct BfsLadder {
+    bool tiny = true;           // start at the LDS tiers
+    bool replay = false;        // heap-replay workspaces
+    uint32_t lattice_only = 0;  // BfsWs::lattice_only
+    std::function<int(int kind)> per_cu;  // resident workgroups per CU of an LDS tier
+    std::function<hipError_t(int kind, const BfsWs& ws, unsigned int* next_item,
+                             const uint32_t* list, const uint32_t* count_dev, uint32_t grid)>
+        launch;
+  };
+  hipError_t run_bfs_ladder(uint32_t count, uint32_t* list, uint32_t* list2, uint32_t* cnt,
+                            const int32_t* status, const BfsLadder& L, hipStream_t stream,
+                            LhsRoute* route, uint32_t* grid_out);
   hipError_t run_lazy_tiny(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
                            const BatchOutDev& out, hipStream_t stream, int tier,
                            const uint32_t* items, uint32_t num_items, unsigned int* ctr,

@@ -144,11 +144,21 @@ struct HostProf {
 // lease (its device outputs kept), compacted to CSR on the device (count, scan, gather:
 // DeviceEngine::compact_paths), then downloaded straight into the caller's result at the
 // shard's string and arc offsets.
+// A lattice shard (fst_compose_frozen_batch): the arena the emitting kernels filled, then --
+// after the sink's compaction -- the shard in FstLhsBatch's layout on the device.
+struct LatShard {
+  std::unique_ptr<DevBuf> item, afin, aaoff, ail, aol, aw, anext, cursor;  // the arena
+  LatticeOutDev arena{};
+  std::unique_ptr<DevBuf> status, soff, start, fin, aoffs, il, ol, w, next;  // compacted
+};
+
 struct Shard {
   int dev = 0;
   uint32_t s0 = 0, s1 = 0;
   DeviceEngine::Lease E;
   std::unique_ptr<DevOut> keep;
+  std::unique_ptr<LatShard> lat;  // lattice entries (keep: the statuses)
+  uint64_t tot2 = 0;              // lattice entries: tot = states, tot2 = arcs
   std::unique_ptr<DevBuf> fail;  // pipelines: the first failing stage per string
   std::unique_ptr<DevBuf> st, off, fin, il, ol, w;
   std::unique_ptr<DevBuf> text;  // text entries: the emitted bytes (fin: the total weights)
@@ -160,12 +170,13 @@ struct Shard {
 // What becomes of a computed shard: `compact` (on the shard's lease, after the engines) brings
 // its result into CSR order on the device and sets S.tot; `alloc` makes the host result once
 // every shard's total is known; `download` copies a shard in at its string range and at the
-// sum of the earlier shards' totals; `finish` closes the offsets.
+// sum of the earlier shards' totals; `finish` closes the offsets.  Two totals each (S.tot,
+// S.tot2): the lattice sink's states and arcs; the label and text sinks use the first alone.
 struct ShardSink {
   std::function<FstError(Shard&)> compact;
-  std::function<bool(uint64_t)> alloc;
-  std::function<FstError(Shard&, uint64_t)> download;
-  std::function<void(uint64_t)> finish;
+  std::function<bool(uint64_t, uint64_t)> alloc;
+  std::function<FstError(Shard&, uint64_t, uint64_t)> download;
+  std::function<void(uint64_t, uint64_t)> finish;
 };
 using ShardCompute = std::function<FstError(Shard&)>;
 
@@ -192,6 +203,24 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
 FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
                      const std::vector<double>& cost, const ShardCompute& compute,
                      FstTextResult* out);
+// ... into a lattice result (fst_compose_frozen_batch): compact_lattices on the device, both
+// offset arrays rebased per shard.
+FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
+                     const std::vector<double>& cost, const ShardCompute& compute,
+                     FstLatticeBatch* out);
+bool alloc_lattice_result(FstLatticeBatch* out, uint32_t num, uint64_t states, uint64_t arcs);
+// The compute steps of a lattice shard: chains from the caller's labels, or general lhs staged
+// as run_lhs_shard stages them; S.lat = the filled arena, S.keep = the statuses.
+FstError run_lattice_chain_shard(Shard& S, FrozenFst& b, const uint32_t* labels,
+                                 const uint64_t* offsets, uint32_t lattice_flags);
+FstError run_lattice_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L,
+                               uint32_t lattice_flags);
+// One engine run into a lattice arena (first size: the estimates, or FSTAMD_LATTICE_ARENA=
+// states,arcs), rerun once the cursors say what the batch needs while an item is OUTPUT_FULL.
+FstError run_lattice_arena(DeviceEngine::Lease& E, DeviceFst& D, const ChainInput& in,
+                           const GraphInput* lhs, uint32_t lattice_flags, uint64_t est_states,
+                           uint64_t est_arcs, std::unique_ptr<LatShard>* lat,
+                           std::unique_ptr<DevOut>* keep);
 FstError run_pipelined(int dev, FrozenFst& b, const uint32_t* labels, const uint64_t* offsets,
                        uint32_t num, uint32_t n, int semantics, uint32_t parts,
                        FstBatchResult* out);

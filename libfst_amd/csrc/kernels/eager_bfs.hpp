@@ -967,7 +967,53 @@ __host__ __device__ constexpr int tiny_waves(int k) { return k == 1 ? 3 : 2; }  
 // (A/B on config 4: with the ~3 KB rhs copied into LDS as well a string took 143 / 288 us
 // instead of 178 / 338 us, but 6 workgroups fit per CU instead of 8: no faster overall)
 
-template <int WG, int kGraph, int kTiny = 0>
+// The lattice batch's emission (kEmit instances, lattice_batch.hip): the item's finished
+// lattice -- N states, A arcs in the tables T (LDS for the tiny tiers, the slab otherwise) --
+// into the batch arena out.lattice describes (device_engine.hpp LatticeOutDev).  Thread 0
+// reserves round4(N) states and round4(A) arcs with one atomicAdd per cursor and broadcasts the
+// two positions through LDS; every array of the item then starts 16-B aligned on both sides
+// (the tables are carved 16-B aligned, capacities are multiples of 4), so the workgroup copies
+// whole 16-B words, consecutive lanes to consecutive words.  The words past N / A inside the
+// rounding are the item's own padding in the arena; nothing reads them.  With `project` the
+// ilabels are copied from aol.  The cursors count on when the arena is full: OUTPUT_FULL.
+template <int WG>
+__device__ void bfs_emit_lattice(const BfsTables& T, uint32_t N, uint32_t A,
+                                 const BatchOutDev& out, uint32_t si, BfsShared& SH) {
+  const LatticeOutDev& lo = *out.lattice;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t Np = (N + 3u) & ~3u, Ap = (A + 3u) & ~3u;
+  if (tid == 0) {
+    SH.best = atomicAdd(lo.cursor, (unsigned long long)Np);
+    SH.red[0] = atomicAdd(lo.cursor + 1, (unsigned long long)Ap);
+  }
+  __syncthreads();
+  const unsigned long long sp = SH.best, ap = SH.red[0];
+  if (sp + Np > lo.state_cap || ap + Ap > lo.arc_cap) {  // uniform
+    if (tid == 0) write_status(out, si, kPathOutputFull, N, A);
+    return;
+  }
+  const auto copy16 = [&](void* dst, const void* src, uint32_t words) {
+    uint4* d = reinterpret_cast<uint4*>(dst);
+    const uint4* s = reinterpret_cast<const uint4*>(src);
+    for (uint32_t i = tid; i < words; i += WG) d[i] = s[i];
+  };
+  copy16(lo.fin + sp, T.nfin, Np / 2);
+  copy16(lo.aoff + sp, T.aoff, Np / 4);
+  copy16(lo.il + ap, lo.project ? T.aol : T.ail, Ap / 4);
+  copy16(lo.ol + ap, T.aol, Ap / 4);
+  copy16(lo.next + ap, T.anext, Ap / 4);
+  copy16(lo.w + ap, T.aw, Ap / 2);
+  if (tid == 0) {
+    uint4* r = reinterpret_cast<uint4*>(lo.item + si);
+    r[0] = make_uint4((uint32_t)sp, (uint32_t)(sp >> 32), (uint32_t)ap, (uint32_t)(ap >> 32));
+    r[1] = make_uint4(N, A, 0u, 0u);
+    write_status(out, si, kPathOk, N, A);
+  }
+}
+
+// kEmit: the lattice batch's instances (the host sets ws.lattice_only): every item's lattice
+// goes to the batch arena (bfs_emit_lattice) instead of staying behind in hdr and the slab.
+template <int WG, int kGraph, int kTiny = 0, bool kEmit = false>
 __global__ void __launch_bounds__(WG, WG == 64 ? (kTiny ? tiny_waves(kTiny) : FSTAMD_BFS_WAVES64) : 1)
 eager_bfs_kernel(RhsView rhs, ChainInput in, GraphInput graph, uint32_t n_best,
                  unsigned int* next_item, const uint32_t* items, const uint32_t* num_items_dev,
@@ -976,6 +1022,7 @@ eager_bfs_kernel(RhsView rhs, ChainInput in, GraphInput graph, uint32_t n_best,
   // and keeps only the tables in LDS)
   static_assert(kTiny == 0 || (kGraph != kLhsGraph && WG == 64),
                 "the tiny tiers are the batches'");
+  static_assert(!kEmit || kGraph != kLhsGraph, "the single call keeps hdr and the slab");
   __shared__ BfsShared SH;
   const uint32_t tid = threadIdx.x;
   BfsTables T;
@@ -1043,7 +1090,14 @@ eager_bfs_kernel(RhsView rhs, ChainInput in, GraphInput graph, uint32_t n_best,
       }
     }
     if (ws.lattice_only && no_start) {  // compose.zig:33-35: empty result
-      if (tid == 0) {
+      if constexpr (kEmit) {  // OK, zero states (the count kernel reads no record of it)
+        if (tid == 0) {
+          uint4* r = reinterpret_cast<uint4*>(out.lattice->item + si);
+          r[0] = make_uint4(0u, 0u, 0u, 0u);
+          r[1] = make_uint4(0u, 0u, 0u, 0u);
+          write_status(out, si, kPathOk, 0, 0);
+        }
+      } else if (tid == 0) {
         hdr[0] = 0;
         hdr[1] = 0;
         hdr[2] = 0;
@@ -1236,7 +1290,13 @@ eager_bfs_kernel(RhsView rhs, ChainInput in, GraphInput graph, uint32_t n_best,
     const bool dag = SH.changed == 0;
 
     if (ws.lattice_only) {
-      if (tid == 0) {
+      if constexpr (kEmit) {
+        if (fail != kPathOk) {  // OVERFLOW: the next tier's; INTERNAL: the watchdog
+          if (tid == 0) write_status(out, si, fail, n_nodes, n_arcs);
+        } else {
+          bfs_emit_lattice<WG>(T, n_nodes, n_arcs, out, si, SH);
+        }
+      } else if (tid == 0) {
         hdr[0] = n_nodes;
         hdr[1] = n_arcs;
         hdr[2] = n_levels;

@@ -83,6 +83,22 @@ class FstDeviceBatch(C.Structure):
                 ("work", C.c_void_p)]
 
 
+FST_LATTICE_PROJECT_OUTPUT = 1
+
+
+class FstLatticeBatch(C.Structure):
+    _fields_ = [("fsts", FstLhsBatch), ("status", C.POINTER(C.c_int32)),
+                ("total_states", C.c_uint64), ("total_arcs", C.c_uint64)]
+
+
+class FstDeviceLattices(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("state_offsets", C.c_void_p), ("start", C.c_void_p),
+                ("final_weights", C.c_void_p), ("arc_offsets", C.c_void_p),
+                ("ilabels", C.c_void_p), ("olabels", C.c_void_p), ("weights", C.c_void_p),
+                ("nextstates", C.c_void_p), ("state_capacity", C.c_uint64),
+                ("arc_capacity", C.c_uint64)]
+
+
 class FstLaunchStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("launches", C.c_uint32), ("engine", C.c_uint32),
                 ("grid", C.c_uint32)]
@@ -139,6 +155,16 @@ SIGNATURES = {
     "fst_device_compose_shortest_path": (
         C.c_int, [_u64, _P, _P, _u32, _u32, _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceBatch), _P]),
+    "fst_compose_frozen_batch": (
+        C.c_int, [_u64, _P, _P, _u32, _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstLatticeBatch)]),
+    "fst_compose_frozen_lhs_batch": (
+        C.c_int, [_u64, C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstLatticeBatch)]),
+    "fst_lattice_batch_free": (None, [C.POINTER(FstLatticeBatch)]),
+    "fst_device_compose_frozen": (
+        C.c_int, [_u64, _P, _P, _u32, _u32, _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstDeviceLattices), C.POINTER(_u64), _P]),
     "fst_device_prepare": (C.c_int, [_u64, _i32]),
     "fst_device_adopt_blob": (_u64, [_P, _u64, _i32, _P]),
     "fst_last_launch_stats": (C.c_int, [C.POINTER(FstLaunchStats)]),
@@ -461,6 +487,100 @@ def compose_frozen_shortest_path_lhs_batch(b: Fst, lhs: LhsBatch, n: int = 1,
     if rc != FST_OK:
         raise RuntimeError(f"fst_compose_frozen_shortest_path_lhs_batch failed: {rc}")
     return _take_result(res, len(lhs))
+
+
+class _LatticeOwner:
+    """Owns one FstLatticeBatch; fst_lattice_batch_free runs once no array views it."""
+
+    def __init__(self, res):
+        self.res = res
+
+    def __del__(self):
+        try:
+            lib().fst_lattice_batch_free(C.byref(self.res))
+        except Exception:  # interpreter shutdown
+            pass
+
+
+class LatticeBatch:
+    """The result of compose_frozen_batch / compose_frozen_lhs_batch: N lattices in
+    FstLhsBatch's layout as numpy views of the library's pinned arrays (no copy; the arrays
+    keep the result alive), and one status per item."""
+
+    def __init__(self, res: FstLatticeBatch):
+        num, ns, na = int(res.fsts.num_fsts), int(res.total_states), int(res.total_arcs)
+        owner = _LatticeOwner(res)
+        self._owner = owner
+
+        def arr(p, cnt, dt, ct):
+            if cnt == 0:
+                return np.zeros(0, dt)
+            buf = (ct * cnt).from_address(C.cast(p, C.c_void_p).value)
+            buf._owner = owner  # the view keeps the result alive
+            return np.frombuffer(buf, dtype=dt)
+
+        f = res.fsts
+        self.status = arr(res.status, num, np.int32, C.c_int32)
+        self.state_offsets = arr(f.state_offsets, num + 1, np.uint64, C.c_uint64)
+        self.start = arr(f.start, num, np.uint32, C.c_uint32)
+        self.final_weights = arr(f.final_weights, ns, np.float64, C.c_double)
+        self.arc_offsets = arr(f.arc_offsets, ns + 1, np.uint64, C.c_uint64)
+        self.ilabels = arr(f.ilabels, na, np.uint32, C.c_uint32)
+        self.olabels = arr(f.olabels, na, np.uint32, C.c_uint32)
+        self.weights = arr(f.weights, na, np.float64, C.c_double)
+        self.nextstates = arr(f.nextstates, na, np.uint32, C.c_uint32)
+
+    def __len__(self):
+        return len(self.status)
+
+    def as_lhs(self) -> LhsBatch:
+        """An LhsBatch over the same memory (its arrays are these views, which keep the
+        library's result alive): the input of every lhs batch entry."""
+        return LhsBatch(self.state_offsets, self.start, self.final_weights, self.arc_offsets,
+                        self.ilabels, self.olabels, self.weights, self.nextstates)
+
+    def item(self, i):
+        """(start, finals, arcs per state) of item i, as MutableFst.to_lists(); start is
+        FST_NO_STATE for an item of zero states."""
+        s0, s1 = int(self.state_offsets[i]), int(self.state_offsets[i + 1])
+        ao = self.arc_offsets[s0:s1 + 1].astype(np.int64)
+        arcs = []
+        for s in range(s1 - s0):
+            a, z = int(ao[s]), int(ao[s + 1])
+            arcs.append(list(zip(self.ilabels[a:z].tolist(), self.olabels[a:z].tolist(),
+                                 self.weights[a:z].tolist(), self.nextstates[a:z].tolist())))
+        return int(self.start[i]), self.final_weights[s0:s1].tolist(), arcs
+
+
+def compose_frozen_batch(b: Fst, labels, offsets, project_output: bool = False, device: int = -1,
+                         devices=None, shards: int = 0) -> LatticeBatch:
+    """fst_compose_frozen for a batch of chains (fst_compose_frozen_batch): item i is the
+    lattice fst_compose_frozen(compile(labels of string i), b) returns, bit for bit."""
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    opts = batch_options(device, FST_SEM_LAZY, devices, shards)
+    res = FstLatticeBatch()
+    rc = lib().fst_compose_frozen_batch(b.h, labels.ctypes.data, offsets.ctypes.data,
+                                        len(offsets) - 1,
+                                        FST_LATTICE_PROJECT_OUTPUT if project_output else 0,
+                                        C.byref(opts), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_compose_frozen_batch failed: {rc}")
+    return LatticeBatch(res)
+
+
+def compose_frozen_lhs_batch(b: Fst, lhs: LhsBatch, project_output: bool = False,
+                             device: int = -1, devices=None, shards: int = 0) -> LatticeBatch:
+    """The same for a batch of general lhs (fst_compose_frozen_lhs_batch)."""
+    opts = batch_options(device, FST_SEM_LAZY, devices, shards)
+    res = FstLatticeBatch()
+    cs = lhs.c_struct()
+    rc = lib().fst_compose_frozen_lhs_batch(b.h, C.byref(cs),
+                                            FST_LATTICE_PROJECT_OUTPUT if project_output else 0,
+                                            C.byref(opts), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_compose_frozen_lhs_batch failed: {rc}")
+    return LatticeBatch(res)
 
 
 def pipeline_lhs_batch(stages, lhs: LhsBatch, n: int = 1, semantics: int = FST_SEM_LAZY,

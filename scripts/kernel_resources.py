@@ -10,7 +10,8 @@ kernel: SGPRs, VGPRs, AGPRs, scratch bytes per lane, spills, waves per SIMD, LDS
 
 Template arguments are printed as the demangler gives them, except that the lhs-kind
 argument of eager_bfs_kernel / lazy_wave_kernel is normalised (false -> 0, true -> 1), so
-listings from before and after that argument became an int compare line by line.
+listings from before and after that argument became an int compare line by line; likewise
+eager_bfs_kernel's fourth argument (lattice emission) is dropped where it is false.
 """
 import argparse
 import os
@@ -36,6 +37,8 @@ def normalise(name):
     word = {"false": "0", "true": "1"}
     name = re.sub(r"eager_bfs_kernel<(\d+), (false|true)",
                   lambda m: f"eager_bfs_kernel<{m.group(1)}, {word[m.group(2)]}", name)
+    # (the emission flag came later still: an instance that does not emit keeps its old name)
+    name = re.sub(r"(eager_bfs_kernel<\d+, \d+, \d+), false>", r"\1>", name)
     name = re.sub(r"lazy_wave_kernel<(false|true)>",
                   lambda m: f"lazy_wave_kernel<{word[m.group(1)]}>", name)
     return re.sub(r"\(.*", "", name)  # the parameter list says nothing the name does not
