@@ -458,6 +458,13 @@ int32_t fst_debug_coalescer_state(int32_t device, uint32_t* queued);
 uint64_t fst_debug_text_compact(uint32_t num_strings, uint64_t* offsets, const uint32_t* nbytes,
                                 int32_t* status, double* total_weight, uint8_t* text);
 
+/* Diagnostics / tests, no GPU needed: the host step of the streamed batch's weight codes.
+ * dst[i] = table[codes[i]] for i < n; table has 256 entries, dst is 8-byte aligned and is
+ * written with non-temporal stores where whole 64-byte lines allow.  Nothing outside
+ * codes[0 .. n), table[0 .. 256) and dst[0 .. n) is read or written. */
+void fst_debug_expand_weight_codes(const uint8_t* codes, uint64_t n, const double* table,
+                                   double* dst);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,7 @@
 // pipelined, sharded), the device-side entries.  (fst_debug_coalescer_state: c_api.cpp.)
 
 #include "host_rt.hpp"
+#include "weight_codes.hpp"
 
 using namespace fstamd;
 using namespace fstamd::host;
@@ -806,6 +807,12 @@ uint64_t fst_debug_text_compact(uint32_t num_strings, uint64_t* offsets, const u
                                 int32_t* status, double* total_weight, uint8_t* text) {
   if (!offsets || (num_strings && (!nbytes || !status || !total_weight))) return 0;
   return text_compact(num_strings, offsets, nbytes, status, total_weight, text);
+}
+
+void fst_debug_expand_weight_codes(const uint8_t* codes, uint64_t n, const double* table,
+                                   double* dst) {
+  if (!n || !codes || !table || !dst) return;
+  expand_weight_codes(codes, (size_t)n, table, dst);
 }
 
 int32_t fst_weight_type(FstHandle b) {

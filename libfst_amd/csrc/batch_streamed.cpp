@@ -22,9 +22,51 @@
 #include <map>
 
 #include "host_rt.hpp"
+#include "weight_codes.hpp"
 
 namespace fstamd::host {
 namespace {
+
+// FSTAMD_STREAM_CODES: 0 = the f64 copy-out for every part, 1 = every part's weights leave
+// as 1-B codes (default), 2 = every part but the last
+int stream_codes_mode() {
+  const char* e = std::getenv("FSTAMD_STREAM_CODES");
+  const int m = e ? std::atoi(e) : 1;
+  return m < 0 || m > 2 ? 1 : m;
+}
+
+// The parts' cuts, per mille of a shard's labels: FSTAMD_STREAM_CUTS, or 1/43 and 7/43 (each
+// part's upload fits in the previous part's compute), and, when every part leaves codes,
+// shrinking parts after the big one, so that little expansion is left after the last kernel.
+std::vector<uint64_t> stream_cuts(bool all_coded) {
+  std::vector<uint64_t> pm{23, 163};
+  if (all_coded) pm = {23, 163, 700, 900, 970};
+  if (const char* ce = std::getenv("FSTAMD_STREAM_CUTS")) {
+    pm.clear();
+    for (const char* q = ce; *q;) {
+      char* e = nullptr;
+      const unsigned long v = std::strtoul(q, &e, 10);
+      if (e == q) break;
+      if (v > 0 && v < 1000) pm.push_back(v);
+      q = *e ? e + 1 : e;
+    }
+  }
+  return pm;
+}
+constexpr size_t kStreamMaxParts = 64;
+
+// a block of the pinned host pool, given back on scope exit
+struct PinBlock {
+  void* p = nullptr;
+  void reset(void* q) {
+    if (p) pin_release(p);
+    p = q;
+  }
+  ~PinBlock() { reset(nullptr); }
+  PinBlock() = default;
+  PinBlock(const PinBlock&) = delete;
+  PinBlock& operator=(const PinBlock&) = delete;
+};
 
 struct StreamKit {  // per calling thread and device: the upload stream and its events
   hipStream_t up = nullptr;
@@ -142,23 +184,29 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
   };
 
   // ---- parts: string ranges cut at these fractions of the labels (per mille; small
-  // shards: one part): 1/43 and 7/43, so each part's upload fits in the previous part's
-  // compute.  FSTAMD_STREAM_CUTS overrides (A/B, one box: "23,163" 30.9 ms per 1M metric
-  // strings, "167" 31.2, "100,400" 31.0, "125" 31.5) ----
+  // shards: one part; stream_cuts).  FSTAMD_STREAM_CUTS overrides (A/B, one box, f64
+  // copy-out: "23,163" 30.9 ms per 1M metric strings, "167" 31.2, "100,400" 31.0, "125"
+  // 31.5) ----
+  // Weight codes: when this rhs, these semantics and this max_len take tier
+  // P's code instances (pull_codes_table: pull_rk / pull_pack decide) the coded parts' weights
+  // cross the link as one byte per arc into a pinned staging block, and expander threads turn
+  // each part's codes into the result's f64 weights once that part's completion event has
+  // passed, while the later parts run.  The last part's expansion stands exposed after the
+  // last kernel, so the coded route ends on shrinking parts.
+  double code_table[256];
+  int codes_mode = tm ? 0 : stream_codes_mode();
+  if (codes_mode && !pull_codes_table(D, semantics, max_len, code_table)) codes_mode = 0;
+  PinBlock staging;  // the shard's codes, indexed like its labels
+  if (codes_mode) {
+    staging.reset(pin_alloc(std::max<uint64_t>(total, 1)));  // (the copy-out stays inside each string)
+    if (!staging.p || !pin_is_pinned(staging.p)) {  // (the pool gave pageable memory)
+      staging.reset(nullptr);
+      codes_mode = 0;
+    }
+  }
   std::vector<uint32_t> cut{0};
   if (total >= (1u << 22) && num >= (1u << 15)) {
-    std::vector<uint64_t> pm{23, 163};
-    if (const char* ce = std::getenv("FSTAMD_STREAM_CUTS")) {
-      pm.clear();
-      for (const char* q = ce; *q;) {
-        char* e = nullptr;
-        const unsigned long v = std::strtoul(q, &e, 10);
-        if (e == q) break;
-        if (v > 0 && v < 1000) pm.push_back(v);
-        q = *e ? e + 1 : e;
-      }
-    }
-    for (uint64_t f : pm) {
+    for (uint64_t f : stream_cuts(codes_mode == 1)) {
       const uint64_t want = total * f / 1000;
       const uint32_t i = (uint32_t)(std::upper_bound(loff, loff + num, want) - loff);
       if (i > cut.back() && i < num) cut.push_back(i);
@@ -166,7 +214,14 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
   }
   cut.push_back(num);
   const size_t parts = cut.size() - 1;
-  if (parts > 64 || !K->events(parts)) return FST_OOM;  // one upload event a part
+  // one upload event and one completion event a part (run_streamed has checked that this
+  // device's kit and events exist before it allocated the result)
+  if (parts > kStreamMaxParts || !K->events(2 * parts)) return FST_OOM;
+  // parts [0, ncoded) leave codes; mode 2: the last part keeps the f64 copy-out
+  const size_t ncoded = codes_mode == 1 ? parts : codes_mode == 2 ? parts - 1 : 0;
+  if (std::getenv("FSTAMD_ROUTE_LOG"))
+    std::fprintf(stderr, "[libfst_amd route] stream: weight codes %s, mode %d, parts %zu\n",
+                 ncoded ? "on" : "off", ncoded ? codes_mode : 0, parts);
 
   // ---- engines and device buffers ----
   DeviceEngine::Lease EA = DeviceEngine::acquire(dev);
@@ -179,6 +234,12 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
       d_first(std::max<size_t>(num, 1) * 4ull), d_ctr(64 * 4);  // item counter per part
   DevOut o(num, total + 4);
   if (!d_lab.p || !d_off.p || !d_first.p || !d_ctr.p || !o.ok()) return FST_OOM;
+  // the device byte arena of the codes (indexed like the path arena)
+  std::unique_ptr<DevBuf> d_codes;
+  if (ncoded) {
+    d_codes = std::make_unique<DevBuf>(std::max<uint64_t>(total, 1));
+    if (!d_codes->p) return FST_OOM;
+  }
   // text mode: byte counts and total weights per string, and one TextOutDev per part (the
   // kernels reach it through BatchOutDev::text), uploaded with the offsets
   // (d_lab4: the widened labels of a shard that hands strings on, allocated only then)
@@ -277,6 +338,67 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
       });
   }
 
+  // ---- the expanders: thread t of T takes the t-th slice of every coded part, in part
+  // order.  It waits (host side) until the part's completion event has been recorded --
+  // synchronising an event nobody recorded yet, or one a previous call left complete, would
+  // return at once -- then for the event itself, and only then reads the part's codes.
+  // Nothing polls memory the device writes.  Joined on every return (declared after the
+  // staging block, the result and the streams' drain). ----
+  struct Recorded {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<char> rec;
+    bool abort = false;
+  } X;
+  X.rec.assign(parts, 0);
+  auto x_abort = [&] {
+    std::lock_guard<std::mutex> g(X.mu);
+    X.abort = true;
+    X.cv.notify_all();
+  };
+  std::atomic<bool> x_failed{false};
+  // (FSTAMD_HOST_PROF: when each part's event passed and when its expansion ended, ms from
+  // the expanders' start, per thread)
+  const bool x_prof = std::getenv("FSTAMD_HOST_PROF") != nullptr;
+  const auto tx0 = std::chrono::steady_clock::now();
+  auto x_ms = [&] {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tx0).count();
+  };
+  std::vector<double> x_ev, x_end;  // [thread * ncoded + part]
+  Threads Ex;
+  if (ncoded) {
+    const char* xe = std::getenv("FSTAMD_STREAM_EXPANDERS");
+    const uint32_t T = (uint32_t)std::min(16, std::max(1, xe ? std::atoi(xe) : 4));
+    const uint8_t* const codes = (const uint8_t*)staging.p;
+    double* const w_out = out->weights + lbase;
+    x_ev.assign(T * ncoded, 0.0);
+    x_end.assign(T * ncoded, 0.0);
+    for (uint32_t t = 0; t < T; ++t)
+      Ex.th.emplace_back([&, t, T, codes, w_out] {
+        if (hipSetDevice(dev) != hipSuccess) {
+          x_failed = true;
+          return;
+        }
+        for (size_t p = 0; p < ncoded; ++p) {
+          {
+            std::unique_lock<std::mutex> g(X.mu);
+            X.cv.wait(g, [&] { return X.abort || X.rec[p]; });
+            if (!X.rec[p]) return;
+          }
+          if (hipEventSynchronize(K->ev[parts + p]) != hipSuccess) {
+            x_failed = true;
+            return;
+          }
+          if (x_prof) x_ev[t * ncoded + p] = x_ms();
+          // (slices cut at 8 elements: whole lines of the weights for all but the ends)
+          const uint64_t a = loff[cut[p]], z = loff[cut[p + 1]], w = z - a;
+          const uint64_t lo = a + ((w * t / T) & ~7ull), hi = t + 1 == T ? z : a + ((w * (t + 1) / T) & ~7ull);
+          if (hi > lo) expand_weight_codes(codes + lo, hi - lo, code_table, w_out + lo);
+          if (x_prof) x_end[t * ncoded + p] = x_ms();
+        }
+      });
+  }
+
   // ---- the parts: engine A takes parts 0, 2, .., engine B 1, 3, .. (A all without B) ----
   std::vector<FstError> perr(parts, FST_OK);
   // (A/B timing only: FSTAMD_STREAM_AB=1 drops the copy-out; the result then lacks paths)
@@ -285,6 +407,7 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
   auto drive = [&](DeviceEngine::Lease& E, hipStream_t s, size_t p0, size_t step) {
     if (hipSetDevice(dev) != hipSuccess) {
       perr[p0] = FST_INVALID_ARG;
+      x_abort();
       return;
     }
     for (size_t p = p0; p < parts; p += step) {
@@ -293,6 +416,7 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
         R.cv.wait(g, [&] { return R.failed || R.n > p; });
         if (R.n <= p) {
           perr[p] = FST_OOM;
+          x_abort();
           return;
         }
       }
@@ -305,24 +429,36 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
       v.path_off += s0;
       v.final_w += s0;
       v.slots = (const uint64_t*)d_off.p + s0;
+      const bool coded = p < ncoded;
       if (tm) {
         v.text = (const TextOutDev*)d_tx->p + p;
+      } else if (coded) {  // the byte arenas in the weights' places (kernels/eager_pull.hpp CODES)
+        v.host_ol = out->olabels + lbase;
+        v.out_w = (double*)d_codes->p;
+        v.host_w = (double*)staging.p;
       } else {
         v.host_ol = out->olabels + lbase;
         v.host_w = out->weights + lbase;
       }
       // (label mode only: without its emission the text route has no result at all)
-      if (ab_nocopy && !tm) v.host_ol = nullptr, v.host_w = nullptr;
+      if (ab_nocopy && !tm && !coded) v.host_ol = nullptr, v.host_w = nullptr;
       v.first_status = (int32_t*)d_first.p + s0;
       // the pull tier alone: no fill, copy or host synchronisation between parts (a fill
       // or copy is a blit kernel that waits for CU slots behind the other engine's
       // persistent kernel, and had held this engine's next part back); the later tiers
       // and the downloads come after the last part
       if (hipStreamWaitEvent(s, K->ev[p], 0) != hipSuccess ||
-          E->launch_pull_part(D, in, n, semantics, v, s, (unsigned int*)d_ctr.p + p, tm) !=
-              hipSuccess) {
+          E->launch_pull_part(D, in, n, semantics, v, s, (unsigned int*)d_ctr.p + p, tm, coded) !=
+              hipSuccess ||
+          (coded && hipEventRecord(K->ev[parts + p], s) != hipSuccess)) {
         perr[p] = FST_OOM;
+        x_abort();
         return;
+      }
+      if (coded) {  // the part's completion event is in the stream: its expanders may wait
+        std::lock_guard<std::mutex> g(X.mu);
+        X.rec[p] = 1;
+        X.cv.notify_all();
       }
     }
   };
@@ -349,7 +485,25 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
            (!with_first || d2h(first, d_first.p, num * 4ull, sA)) &&
            hipStreamSynchronize(sA) == hipSuccess;
   };
+  // (an error return here leaves expanders in flight: they are joined on the way out)
   if (!download(true) || fault_inject("stream_after_pull")) return FST_OOM;
+  // the expanders, before anything else writes the result's weights: what the later tiers
+  // finish is downloaded over whatever the expanders made of those strings' unwritten codes
+  Ex.join();
+  if (x_failed) return FST_OOM;
+  if (x_prof && ncoded) {
+    const size_t T = x_ev.size() / ncoded;
+    for (size_t p = 0; p < ncoded; ++p) {
+      double e0 = x_ev[p], e1 = 0;
+      for (size_t t = 0; t < T; ++t) {
+        e0 = std::min(e0, x_ev[t * ncoded + p]);
+        e1 = std::max(e1, x_end[t * ncoded + p]);
+      }
+      std::fprintf(stderr, "[libfst_amd stream] part %zu labels %llu event +%.3f ms expanded +%.3f ms\n",
+                   p, (unsigned long long)(loff[cut[p + 1]] - loff[cut[p]]), e0, e1);
+    }
+    std::fprintf(stderr, "[libfst_amd stream] expanders joined +%.3f ms\n", x_ms());
+  }
   // the later tiers, once, over the strings the pull tier handed on (in the device arena,
   // the same slots) -- only when it handed some on (the metric: none), then the statuses
   // and final weights again
@@ -410,6 +564,15 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
            d2h(out->weights + lbase, vb.out_w, total * 8, sA);
     }
     if (!ok || hipStreamSynchronize(sA) != hipSuccess) return FST_OOM;
+    // ... but not the weights of the coded parts' pull-tier paths: those exist as codes
+    // alone, and are expanded again over what the bulk download put in their slots
+    if (nfix > few && ncoded)
+      for (uint32_t i = 0; i < cut[ncoded]; ++i)
+        if (first[i] == kPathOk) {
+          const uint64_t a = loff[i], L = loff[i + 1] - a;
+          expand_weight_codes((const uint8_t*)staging.p + a, L, code_table,
+                              out->weights + lbase + a);
+        }
   }
   Th.join();
   S.launches = launches;
@@ -467,6 +630,16 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b, St
     if (!Ds[d]) return FST_OOM;
     if (Ds[d]->has_eps || !DeviceEngine::pull_first(*Ds[d], semantics))
       return kStreamNotApplicable;
+  }
+  // before the result exists: a call with more parts than the route takes, or whose stream
+  // kit or events cannot be created, goes the pipelined way instead of failing
+  {
+    const size_t max_parts = std::max(stream_cuts(false).size(), stream_cuts(true).size()) + 1;
+    if (max_parts > kStreamMaxParts) return kStreamNotApplicable;
+    for (int dev : devices) {
+      KitLease K(dev);
+      if (!K || !K->events(2 * max_parts)) return kStreamNotApplicable;
+    }
   }
   const uint64_t base0 = offsets[0], total = offsets[num] - base0;
   if (tm) {

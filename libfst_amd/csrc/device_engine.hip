@@ -1370,7 +1370,8 @@ hipError_t DeviceEngine::run_lazy_pull(const DeviceFst& rhs, const ChainInput& i
 
 hipError_t DeviceEngine::launch_pull_part(const DeviceFst& rhs, const ChainInput& in,
                                           uint32_t n, int semantics, const BatchOutDev& out,
-                                          hipStream_t stream, unsigned int* item_ctr, bool text) {
+                                          hipStream_t stream, unsigned int* item_ctr, bool text,
+                                          bool codes) {
   HIP_TRY(hipSetDevice(dev_));
   if (!pull_first(rhs, semantics)) return hipErrorInvalidValue;
   // text: the text emission writes each string's fixed slot, and there is no path copy-out.
@@ -1378,9 +1379,13 @@ hipError_t DeviceEngine::launch_pull_part(const DeviceFst& rhs, const ChainInput
   if (text ? (!out.text || !out.slots || out.host_ol) : (out.host_w && !out.host_ol))
     return hipErrorInvalidValue;
   if (!in.labels) return hipErrorInvalidValue;  // (or the bytes: the same place)
-  if (in.num_strings == 0) return hipSuccess;
   const bool lazy = semantics != 1;
+  // codes: eager label batches with every array of the code copy-out in place
+  if (codes && (text || lazy || !out.slots || !out.host_ol || !out.host_w || !out.out_w))
+    return hipErrorInvalidValue;
+  if (in.num_strings == 0) return hipSuccess;
   const int per_cu = text   ? text_pull_waves_per_cu(rhs, in.max_len, lazy)
+                     : codes ? code_pull_waves_per_cu(rhs, in.max_len)
                      : lazy ? lazy_pull_waves_per_cu(rhs, in.max_len)
                             : pull_waves_per_cu(rhs, in.max_len);
   const uint32_t back_cap =
@@ -1390,7 +1395,9 @@ hipError_t DeviceEngine::launch_pull_part(const DeviceFst& rhs, const ChainInput
   uint32_t full = (uint32_t)std::max<uint64_t>((uint64_t)per_cu * num_cus_, 1);
   // (tests of the text batch: a few waves take every string, so every emission runs with
   // jobs pending; the label batch's parts take no such cap, as before)
-  if (text) full = std::min<uint32_t>(full, grid_cap(lazy ? "FSTAMD_LP_GRID" : "FSTAMD_P_GRID"));
+  // (and of the weight codes)
+  if (text || codes)
+    full = std::min<uint32_t>(full, grid_cap(lazy ? "FSTAMD_LP_GRID" : "FSTAMD_P_GRID"));
   while (full > 1 && (uint64_t)full * kChaseBatch * back_cap * 8 > (24ull << 30)) full /= 2;
   uint2* back = (uint2*)scratch(lazy ? kLpBack : kPullBack, (size_t)full * kChaseBatch * back_cap * 8);
   if (!back) return hipErrorOutOfMemory;
@@ -1399,6 +1406,7 @@ hipError_t DeviceEngine::launch_pull_part(const DeviceFst& rhs, const ChainInput
   if (text)
     return lazy ? launch_lazy_pull_text(rhs, in, n, item_ctr, lp, out, grid, stream)
                 : launch_eager_pull_text(rhs, in, n, item_ctr, lp, out, grid, stream);
+  if (codes) return launch_eager_pull_codes(rhs, in, n, item_ctr, lp, out, grid, stream);
   return lazy ? launch_lazy_pull(rhs, in, n, item_ctr, lp, out, grid, stream)
               : launch_eager_pull(rhs, in, n, item_ctr, lp, out, grid, stream);
 }

@@ -161,6 +161,9 @@ struct DeviceFst {
   // one byte, the in-arc's position x * kp + m in its target's group (the chases re-derive
   // the record from the target state: tier P with rrec4, the lazy pull with any records)
   bool byte_back = false;
+  // the host's copy of the RK 4 / 5 weight table (kPullWtMax entries, what rv_weight_table
+  // holds on the device): the streamed batch expands weight codes with it
+  std::vector<double> wtab_host;
   // Routing hints learnt from earlier batches on this rhs: a small-lattice (LDS) tier that
   // handed on nearly every string is skipped next time (config 3's lattices never fit).
   mutable std::atomic<int> skip_tiny_lazy{0}, skip_tiny_eager{0};
@@ -412,6 +415,19 @@ hipError_t launch_eager_pull_text(const DeviceFst& rhs, const ChainInput& in, ui
 hipError_t launch_lazy_pull_text(const DeviceFst& rhs, const ChainInput& in, uint32_t n_best,
                                  unsigned int* next_item, const EagerLaunch& lp,
                                  const BatchOutDev& out, uint32_t grid, hipStream_t stream);
+// Tier P's weight-code instances (code_pull.hip; the streamed label batch).  pull_codes_table:
+// whether this rhs, these semantics and this max_len take them -- eager semantics and records
+// that hold the weight as a byte (RK 2..6; it follows pull_rk / pull_pack, the single
+// decision) -- and if so the 256 f64 values the codes stand for: (double)c * RevView::winv
+// for the integer kinds, the rhs's weight table for RK 4 and 5.  They are the values the f64
+// chase writes, bit for bit.  Then resident waves per CU and the launch: out.out_w holds the
+// device byte arena and out.host_w the host's code staging block (both indexed like the
+// path arena, 4-B aligned bases), out.host_ol the result's olabels.
+bool pull_codes_table(const DeviceFst& rhs, int semantics, uint32_t max_len, double* table);
+int code_pull_waves_per_cu(const DeviceFst& rhs, uint32_t max_len);
+hipError_t launch_eager_pull_codes(const DeviceFst& rhs, const ChainInput& in, uint32_t n_best,
+                                   unsigned int* next_item, const EagerLaunch& lp,
+                                   const BatchOutDev& out, uint32_t grid, hipStream_t stream);
 // Lazy pull tier (eager_pull.hip, kernels/lazy_pull.hpp): resident waves per CU, launch.
 int lazy_pull_waves_per_cu(const DeviceFst& rhs, uint32_t max_len);
 bool lazy_pull_f32(const DeviceFst& rhs, uint32_t max_len);
@@ -567,7 +583,9 @@ class DeviceEngine {
   // then run once over the whole batch: run_chain with set_after_pull(true).
   hipError_t launch_pull_part(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
                               int semantics, const BatchOutDev& out, hipStream_t stream,
-                              unsigned int* item_ctr, bool text = false);
+                              unsigned int* item_ctr, bool text = false, bool codes = false);
+  // codes = true (the streamed label batch, pull_codes_table holds): tier P's weight-code
+  // instance; out.out_w / out.host_w hold the byte arenas (launch_eager_pull_codes).
   // text = true (the streamed text batch): `in` holds bytes (ChainInput::text), `out` the
   // text outputs (BatchOutDev::text, with slots and without host_ol), and the pull tier's
   // text instance runs.  Otherwise host_w without host_ol is refused: it shares text's place.

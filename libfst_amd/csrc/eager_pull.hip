@@ -24,6 +24,7 @@ void free_reverse_mirror(DeviceFst* d) {
   d->pull_ok = false;
   d->widx = false;
   d->wt_n = 0;
+  d->wtab_host.clear();
   d->pack = false;
 }
 
@@ -307,6 +308,7 @@ bool build_reverse_mirror(DeviceFst* d, const FrozenFst& f) {
   if (!wtab.empty()) {  // appended to the records (rv_weight_table)
     d->wt_n = (uint32_t)wtab.size();
     wtab.resize(kPullWtMax, 0.0);
+    d->wtab_host = wtab;
     rrec4.resize((rrec4.size() + 1) & ~(size_t)1, 0xFFFF0000u);
     const size_t at = rrec4.size();
     rrec4.resize(at + 2 * kPullWtMax);

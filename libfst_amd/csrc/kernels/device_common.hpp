@@ -163,6 +163,41 @@ __device__ __forceinline__ void copy_out_paths(const BatchOutDev& out, uint32_t 
 }
 #endif
 
+// copy_out_paths' sibling for the weight codes (the CODES instances of tier P, code_pull.hip):
+// the olabels go out as above; the weights are one byte per arc in a device byte arena in
+// out_w's place, and go to the host's code staging block in host_w's place.  Both are
+// indexed like the path arena and share every byte's address modulo 4 (both bases are
+// 4-B aligned), so the middle of a string's codes goes out as dwords -- at L = 64 on an
+// aligned slot 16 lanes write one 64-B line -- and the head and tail bytes before / after it
+// one byte per lane in the same pass.
+__device__ __forceinline__ void copy_out_codes(const BatchOutDev& out, uint32_t njobs,
+                                               uint64_t my_o, uint32_t my_L, uint32_t lane) {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  const uint8_t* const dcode = reinterpret_cast<const uint8_t*>(out.out_w);
+  uint8_t* const hcode = reinterpret_cast<uint8_t*>(out.host_w);
+  for (uint32_t j = 0; j < njobs; ++j) {  // uniform
+    const uint32_t Lj = __builtin_amdgcn_readlane(my_L, j);
+    const uint64_t oj = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(my_o >> 32), j) << 32) |
+                        (uint32_t)__builtin_amdgcn_readlane((uint32_t)my_o, j);
+    for (uint32_t x = lane; x < Lj; x += 64)
+      __builtin_nontemporal_store(out.out_ol[oj + x], out.host_ol + oj + x);
+    // codes: hd head bytes, nq dwords, then the tail bytes
+    const uint32_t hd = min(Lj, (4u - ((uint32_t)oj & 3u)) & 3u);
+    const uint32_t nq = (Lj - hd) >> 2, tl = Lj - hd - 4 * nq;
+    for (uint32_t u = lane; u < nq + hd + tl; u += 64) {
+      if (u < nq) {
+        const uint64_t at = oj + hd + 4ull * u;
+        __builtin_nontemporal_store(*reinterpret_cast<const uint32_t*>(dcode + at),
+                                    reinterpret_cast<uint32_t*>(hcode + at));
+      } else {
+        const uint32_t r = u - nq;
+        const uint64_t at = oj + (r < hd ? r : 4 * nq + r);
+        __builtin_nontemporal_store(dcode[at], hcode + at);
+      }
+    }
+  }
+}
+
 // Streamed text batches (BatchOutDev::text), in copy_out_paths' place: after a batched chase
 // (or, for the strings the later tiers finished, from text_fixup_kernel with one job) lane j
 // < njobs holds job j -- string my_si, arena slot my_o, my_L arcs, final weight my_fw -- and

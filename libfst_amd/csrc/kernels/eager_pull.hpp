@@ -286,7 +286,14 @@ __device__ __forceinline__ void pull_group(const RevView& rv, uint32_t lab, uint
 // label = byte + 1) and every batched chase ends with the text emission (BatchOutDev::text,
 // emit_text_paths) instead of the path copy-out; no ilabels are written.  A compile-time
 // axis in a translation unit of its own: the label instances' code is untouched by it.
-template <int EW, int KP, bool DIRECT, int WAVES_PER_EU, int RK = 0, bool TEXT = false>
+// CODES (the streamed label batch's weight codes, code_pull.hip; RK 2..6 only): the chase
+// stores the weight byte it already holds -- the integer weight of RK 2, 3 and 6, the table
+// index of RK 4 and 5 -- into a byte arena indexed like the path arena, in out_w's place, and
+// the copy-out sends those bytes to the host's code staging block, in host_w's place
+// (copy_out_codes); the host turns them into the same f64 bit patterns.  A compile-time axis
+// in a translation unit of its own, as TEXT is.
+template <int EW, int KP, bool DIRECT, int WAVES_PER_EU, int RK = 0, bool TEXT = false,
+          bool CODES = false>
 __global__ void __launch_bounds__(64, WAVES_PER_EU)
 eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
                   unsigned int* next_item, EagerLaunch lp, BatchOutDev out) {
@@ -295,6 +302,7 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
   constexpr bool REC4 = RK >= 3;  // tier P's 4-B records (RK 4 / 5: f64 cells)
   constexpr bool PACK = RK == 6;  // RK 3 with packed (distance, key) cells
   static_assert(!PACK || (DIRECT && KP < (int)kPackPadM), "packed cells: direct layout, m = 15 is padding");
+  static_assert(!CODES || (RK >= 2 && RK <= 6 && !TEXT), "weight codes: byte-weight records, label batches");
   constexpr int WT = RK == 5 ? (int)kPullWtMax : (int)kPullWt;  // weight-table entries
   using DT = typename std::conditional<F32, uint32_t, double>::type;  // (F32: integer cells)
   using RT = typename std::conditional<
@@ -375,13 +383,19 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         if constexpr (PACK) {
           const uint32_t r = rpk[b];
           out.out_ol[jb.o + k] = rv.rolab[b];
+          if constexpr (CODES)
+            reinterpret_cast<uint8_t*>(out.out_w)[jb.o + k] = (uint8_t)(r >> 16);
+          else
           out.out_w[jb.o + k] = (double)((r >> 16) & 0xFFu) * rv.winv;  // exact: the f64 weight
           tcur = tcur - (r >> 26) + (rv.rbias8 >> 3);  // the source: delta4 / 4 states back
           src8 = tcur << 3;
         } else if constexpr (REC4) {
           const uint32_t r = rv.rrec4[b];
           out.out_ol[jb.o + k] = rv.rolab[b];
-          if constexpr (RK >= 4)
+          if constexpr (CODES)  // (RK 4 / 5: the table index; RK 3: the integer weight)
+            reinterpret_cast<uint8_t*>(out.out_w)[jb.o + k] =
+                (uint8_t)(RK >= 4 ? r & (WT - 1u) : r & 0xFFu);
+          else if constexpr (RK >= 4)
             out.out_w[jb.o + k] = rv_weight_table(rv)[r & (WT - 1u)];  // the f64 weight
           else
             out.out_w[jb.o + k] = (double)(r & 0xFFu) * rv.winv;  // exact: the f64 weight
@@ -390,6 +404,9 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         } else if constexpr (RK == 2) {
           const uint2 r = rv.rrec8[b];
           out.out_ol[jb.o + k] = rv.rolab[b];
+          if constexpr (CODES)
+            reinterpret_cast<uint8_t*>(out.out_w)[jb.o + k] = (uint8_t)rec8_weight(r.y);
+          else
           out.out_w[jb.o + k] = (double)rec8_weight(r.y) * rv.winv;  // exact: the f64 weight
           src8 = r.x;
         } else if constexpr (F32) {
@@ -419,6 +436,7 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
     }
     if constexpr (TEXT)
       emit_text_paths(out, *out.text, njobs, jb.si, jb.o, jb.L, jb.fw, lane, in.num_strings);
+    else if constexpr (CODES) copy_out_codes(out, njobs, jb.o, jb.L, lane);
     else if (out.host_ol) copy_out_paths(out, njobs, jb.o, jb.L, lane);
     njobs = 0;
     wave_lds_sync();

@@ -3,7 +3,8 @@
 // instances: eager_pull.hip (TEXT = false: label inputs, every caller but one) and
 // text_pull.hip (TEXT = true: the streamed text batch's byte inputs and text emission).  The
 // text instances are a compile-time axis in a file of their own, so the label instances'
-// code -- and eager_pull.hip's compile time -- stay what they were without them.
+// code -- and eager_pull.hip's compile time -- stay what they were without them.  So are the
+// weight-code instances of tier P (CODES = true, code_pull.hip).
 #pragma once
 
 #include <cstdio>
@@ -21,10 +22,10 @@ namespace {
 // 8-record blocks need 4.
 
 // RK: the records the kernel reads -- 0 RevRec (f64 cells), 1 rrec32, 2 rrec8 (f32 cells)
-template <int KP, int WV, int RK, bool TEXT>
+template <int KP, int WV, int RK, bool TEXT, bool CODES = false>
 const void* pull_kernel_ptr(bool direct) {
-  return direct ? (const void*)eager_pull_kernel<kPullRows, KP, true, WV, RK, TEXT>
-                : (const void*)eager_pull_kernel<kPullRows, KP, false, WV, RK, TEXT>;
+  return direct ? (const void*)eager_pull_kernel<kPullRows, KP, true, WV, RK, TEXT, CODES>
+                : (const void*)eager_pull_kernel<kPullRows, KP, false, WV, RK, TEXT, CODES>;
 }
 #ifndef FSTAMD_PULL_WAVES_SMALL  // A/B builds: waves per SIMD for blocks of <= 5 records
 #define FSTAMD_PULL_WAVES_SMALL 5
@@ -41,23 +42,23 @@ const void* pull_kernel_ptr(bool direct) {
 #ifndef FSTAMD_PULL_WAVES_PACK  // A/B builds: the same with packed cells (RK 6)
 #define FSTAMD_PULL_WAVES_PACK FSTAMD_PULL_WAVES_R8
 #endif
-template <int RK, bool TEXT>
+template <int RK, bool TEXT, bool CODES = false>
 const void* pull_kernel_for(const RevView& rv) {
   const bool dir = rv.direct != 0;
   if constexpr (RK == 6) {  // (the direct layout only: DeviceFst::pack)
     switch (rv.kp) {
-      case 4: return (const void*)eager_pull_kernel<kPullRows, 4, true, FSTAMD_PULL_WAVES_PACK, 6, TEXT>;
-      case 5: return (const void*)eager_pull_kernel<kPullRows, 5, true, FSTAMD_PULL_WAVES_PACK, 6, TEXT>;
-      default: return (const void*)eager_pull_kernel<kPullRows, 8, true, 4, 6, TEXT>;
+      case 4: return (const void*)eager_pull_kernel<kPullRows, 4, true, FSTAMD_PULL_WAVES_PACK, 6, TEXT, CODES>;
+      case 5: return (const void*)eager_pull_kernel<kPullRows, 5, true, FSTAMD_PULL_WAVES_PACK, 6, TEXT, CODES>;
+      default: return (const void*)eager_pull_kernel<kPullRows, 8, true, 4, 6, TEXT, CODES>;
     }
   } else {
     constexpr int wv = RK == 5 ? 4  // (f64 cells and a 2 KB weight table: 8.9 KB of LDS)
                      : RK == 4 ? FSTAMD_PULL_WAVES_SMALL  // (f64 cells)
                      : RK >= 2 ? FSTAMD_PULL_WAVES_R8 : RK ? FSTAMD_PULL_WAVES_F32 : FSTAMD_PULL_WAVES_SMALL;
     switch (rv.kp) {
-      case 4: return pull_kernel_ptr<4, wv, RK, TEXT>(dir);
-      case 5: return pull_kernel_ptr<5, wv, RK, TEXT>(dir);
-      default: return pull_kernel_ptr<8, 4, RK, TEXT>(dir);
+      case 4: return pull_kernel_ptr<4, wv, RK, TEXT, CODES>(dir);
+      case 5: return pull_kernel_ptr<5, wv, RK, TEXT, CODES>(dir);
+      default: return pull_kernel_ptr<8, 4, RK, TEXT, CODES>(dir);
     }
   }
 }

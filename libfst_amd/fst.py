@@ -191,6 +191,7 @@ SIGNATURES = {
     "fst_batch_result_to_text": (C.c_int, [C.POINTER(FstBatchResult), C.POINTER(FstTextResult)]),
     "fst_debug_text_compact": (_u64, [_u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "fst_debug_expand_weight_codes": (None, [C.c_void_p, _u64, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -792,6 +793,18 @@ def debug_text_compact(slots, nbytes, status, total_weight, text):
                                          status.ctypes.data, total_weight.ctypes.data,
                                          text.ctypes.data)
     return offsets, status, total_weight, text, int(total)
+
+
+def debug_expand_weight_codes(codes, table, dst):
+    """The streamed batch's host expander (fst_debug_expand_weight_codes): dst[i] =
+    table[codes[i]], written in place into `dst` (a float64 array view of len(codes)
+    elements, any 8-byte aligned start).  Runs without a GPU."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    assert table.shape == (256,) and dst.dtype == np.float64 and dst.flags.c_contiguous
+    assert dst.shape == codes.shape and dst.flags.writeable
+    lib().fst_debug_expand_weight_codes(codes.ctypes.data, codes.size, table.ctypes.data,
+                                        dst.ctypes.data)
 
 
 def coalescer_state(device: int = 0):

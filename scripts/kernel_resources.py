@@ -11,7 +11,8 @@ kernel: SGPRs, VGPRs, AGPRs, scratch bytes per lane, spills, waves per SIMD, LDS
 Template arguments are printed as the demangler gives them, except that the lhs-kind
 argument of eager_bfs_kernel / lazy_wave_kernel is normalised (false -> 0, true -> 1), so
 listings from before and after that argument became an int compare line by line; likewise
-eager_bfs_kernel's fourth argument (lattice emission) is dropped where it is false.
+eager_bfs_kernel's fourth argument (lattice emission) and eager_pull_kernel's seventh (weight
+codes) are dropped where they are false.
 """
 import argparse
 import os
@@ -41,6 +42,8 @@ def normalise(name):
     name = re.sub(r"(eager_bfs_kernel<\d+, \d+, \d+), false>", r"\1>", name)
     name = re.sub(r"lazy_wave_kernel<(false|true)>",
                   lambda m: f"lazy_wave_kernel<{word[m.group(1)]}>", name)
+    # (eager_pull_kernel's seventh argument, the weight codes: likewise dropped where false)
+    name = re.sub(r"(eager_pull_kernel<(?:[^,<>]+, ){5}[^,<>]+), false>", r"\1>", name)
     return re.sub(r"\(.*", "", name)  # the parameter list says nothing the name does not
 
 
