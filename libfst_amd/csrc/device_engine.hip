@@ -352,11 +352,55 @@ constexpr int kEwinKmax = 5;
 constexpr int kEwinWaves = 3;
 static_assert((uint32_t)kEwinW == kPullW, "tiers P and A0 share the back slab geometry");
 
-// Item counters and list counts, one 256-B block shared by the engines (word ranges):
-// run_chain [0..6] and [14..15] (pull tier), run_lazy_pull [34..35], lazy replay retry
-// tiers [6..13], run_bfs_chain [8..11] (never in the
-// same call as the replay tiers), run_lazy_layered [32], run_lazy_dense [33].
+// Item counters and list counts: one block of 64 words (scratch kCounter).  A leased engine
+// serves one entry point at a time on one stream, so two owners of a word can only meet
+// inside one call.  The table: word = owner; who zeroes it.  "prologue" = the first
+// kCtrPrologueWords words, zeroed by run_chain, run_graph, run_lhs_batch, run_lattice_batch
+// and compose_lattice before anything else.
 constexpr size_t kCounterBytes = 256;
+enum Ctr : uint32_t {
+  // eager tiers (route_eager_tiers): item counters of tiers A, B, C, A0, P and the lengths of
+  // the lists between them; prologue
+  kCtrItemA = 0, kCtrItemB = 1, kCtrItemC = 2, kCtrListAB = 3, kCtrListBC = 4, kCtrItemA0 = 5,
+  kCtrListWA = 6, kCtrItemP = 14, kCtrListPW = 15,
+  // item counter of the hashed route's first launch, of run_graph and of compose_lattice;
+  // prologue.  Word 0 again: chain_route picks one route per call, the others are other entries
+  kCtrItemFirst = 0,
+  // hashed route (route_lazy_hashed), retry tiers 1..4: ctr_retry(t) = the item counter, the
+  // next word the list count, words 6..13; the route, per tier.  It never runs the eager tiers
+  // (word 6) or the ladder (words 8..10)
+  kCtrRetry = 6,
+  // run_lhs_batch, lazy (another entry point): item counter and the two list counts; prologue,
+  // then per tier.  It has no ladder (word 9), the eager lhs batch no hashed tiers
+  kCtrLhsLazyItem = 6, kCtrLhsLazyListA = 7, kCtrLhsLazyListB = 9,
+  // the BFS tier ladder (run_bfs_ladder): |list|, item counter, |next list|; its callers
+  // (run_bfs_chain, run_lhs_eager, run_lattice_batch) zero kCtrBfsWords words from
+  // kCtrBfsCount.  That clears words 14..15 too: after the eager tiers on the stream
+  kCtrBfsCount = 8, kCtrBfsItem = 9, kCtrBfsNext = 10,
+  // project_output: the longest projection; zeroed there.  It runs between two stages, after
+  // the first one's run_chain (word 15 as kCtrListPW) has been synchronised
+  kCtrProjMaxLen = 15,
+  kCtrPrologueWords = 16,
+  // item counters of run_lazy_layered, run_lazy_dense, run_lazy_band; each per launch
+  kCtrLayeredItem = 32, kCtrDenseItem = 33, kCtrBandItem = 36,
+  // run_lazy_pull: item counter, length of the list it hands on; zeroed there
+  kCtrLazyPullItem = 34, kCtrLazyPullList = 35,
+  // dense route's LDS replays (lazy_lds_sizes): item counter and hand-over length per size,
+  // the outliers' hashed replay's item counter; 40..43 once at its start, the others per launch
+  kCtrLds128Item = 40, kCtrLds128List = 41, kCtrLds256Item = 42, kCtrLds256List = 43,
+  kCtrLdsHashedItem = 44, kCtrLds512Item = 48, kCtrLds512List = 49, kCtrLds1024Item = 50,
+  kCtrLds1024List = 51,
+  // dense route: what a band replay pass hands on; per pass
+  kCtrBandList = 46,
+  kCtrWords = 52
+};
+constexpr uint32_t kCtrBfsWords = 8;
+constexpr uint32_t ctr_retry(int tier) { return kCtrRetry + 2 * (uint32_t)(tier - 1); }
+constexpr uint32_t ctr_retry_list(int tier) { return ctr_retry(tier) + 1; }
+static_assert(kCtrWords * 4 <= kCounterBytes, "every slot lies in the block");
+static_assert(kCtrListPW < kCtrPrologueWords && ctr_retry_list(4) < kCtrPrologueWords &&
+                  kCtrBfsCount + kCtrBfsWords == kCtrPrologueWords,
+              "the eager tiers, the retry tiers and the ladder stay in the prologue's span");
 
 enum Scratch : size_t {
   kCounter = 0,
@@ -690,28 +734,80 @@ static uint32_t grid_cap(const char* env) {
   return g && std::atoi(g) > 0 ? (uint32_t)std::atoi(g) : 0xFFFFFFFFu;
 }
 
-__global__ void collect_list_kernel(const uint32_t* in_list, const uint32_t* in_count,
-                                    const int32_t* status, int32_t code, uint32_t* list,
-                                    uint32_t* count);
+// ---- hand-over between tiers: the strings a tier left OVERFLOW, as a device list ---------
 
-static hipError_t finish_stats(hipEvent_t e0, hipEvent_t e1, LaunchStats* stats) {
-  if (!stats || stats->defer) return hipSuccess;  // (defer: DeviceEngine::finish_deferred)
-  HIP_TRY(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-  stats->kernel_ms = ms;
-  return hipSuccess;
+__global__ void collect_status2_kernel(const int32_t* status, uint32_t num, int32_t a, int32_t b,
+                                       uint32_t* list, uint32_t* count) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < num && (status[i] == a || status[i] == b)) list[atomicAdd(count, 1u)] = i;
 }
 
-bool DeviceEngine::pull_first(const DeviceFst& rhs, int semantics) {
-  if (rhs.has_eps) return false;
-  if (semantics == 1) {  // run_chain's eager tier chain: use_p
-    if (rhs.nan || !rhs.nonneg || !rhs.pull_ok) return false;
-    return std::getenv("FSTAMD_EAGER_TIER1") == nullptr;
-  }
-  const char* le = std::getenv("FSTAMD_LAZY_ENGINE");  // the lazy dispatch below: use_lp
-  if (le && *le) return false;
-  return rhs.nonneg && rhs.finite && rhs.lazy_pull_ok;
+__global__ void collect_list_kernel(const uint32_t* in_list, const uint32_t* in_count,
+                                    const int32_t* status, int32_t code, uint32_t* list,
+                                    uint32_t* count) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < *in_count && status[in_list[i]] == code) list[atomicAdd(count, 1u)] = in_list[i];
+}
+
+namespace {
+// Where a hand-over looks: every string of [0, n) whose status is `a` (with_status:
+// collect_status_kernel) or `a` or `b` (with_status2: collect_status2_kernel, also where
+// a == b), or the members of an earlier list with status OVERFLOW (from_list: its device
+// count, and n = that count as the host knows it, > 0 in every case).
+struct HandSrc {
+  const uint32_t* list;
+  const uint32_t* count_dev;
+  uint32_t n;
+  int32_t a, b;
+  bool pair;
+};
+HandSrc with_status(uint32_t n, int32_t a = kPathOverflow) { return {nullptr, nullptr, n, a, a, false}; }
+HandSrc with_status2(uint32_t n, int32_t a, int32_t b) { return {nullptr, nullptr, n, a, b, true}; }
+HandSrc from_list(const uint32_t* list, const uint32_t* count_dev, uint32_t n) {
+  return {list, count_dev, n, kPathOverflow, kPathOverflow, false};
+}
+
+// The collect half: queues the kernel that writes src's strings to `dst` and adds their
+// number to *count_dev (zeroed by the caller).  No copy, no wait.
+hipError_t collect(const HandSrc& s, const int32_t* status, uint32_t* dst, uint32_t* count_dev,
+                   hipStream_t stream) {
+  const uint32_t blocks = (s.n + 255) / 256;
+  if (s.list)
+    collect_list_kernel<<<blocks, 256, 0, stream>>>(s.list, s.count_dev, status, s.a, dst,
+                                                    count_dev);
+  else if (s.pair)
+    collect_status2_kernel<<<blocks, 256, 0, stream>>>(status, s.n, s.a, s.b, dst, count_dev);
+  else
+    collect_status_kernel<<<blocks, 256, 0, stream>>>(status, s.n, s.a, dst, count_dev);
+  return hipGetLastError();
+}
+
+// The whole step: collect, the count back in *host_count, and the wait for it.  mirror: a
+// device word that takes the count as well, before the wait (the ladder's current list).
+hipError_t hand_on(const HandSrc& s, const int32_t* status, uint32_t* dst, uint32_t* count_dev,
+                   uint32_t* host_count, hipStream_t stream, uint32_t* mirror = nullptr) {
+  HIP_TRY(collect(s, status, dst, count_dev, stream));
+  HIP_TRY(hipMemcpyAsync(host_count, count_dev, 4, hipMemcpyDeviceToHost, stream));
+  if (mirror) HIP_TRY(hipMemcpyAsync(mirror, count_dev, 4, hipMemcpyDeviceToDevice, stream));
+  return hipStreamSynchronize(stream);
+}
+}  // namespace
+
+// The stats bracket of every entry point: ev0_, the body's launches, ev1_, kernel_ms.  The
+// body returns early (hipSuccess) where a test hook ends a route; an error leaves at once,
+// without ev1_.  Without stats it only runs the body.
+template <class F>
+hipError_t DeviceEngine::timed(LaunchStats* stats, hipStream_t stream, F&& body) {
+  if (stats) HIP_TRY(hipEventRecord(ev0_, stream));
+  HIP_TRY(body());
+  if (!stats) return hipSuccess;
+  HIP_TRY(hipEventRecord(ev1_, stream));
+  if (stats->defer) return hipSuccess;  // (the caller waits: DeviceEngine::finish_deferred)
+  HIP_TRY(hipEventSynchronize(ev1_));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, ev0_, ev1_));
+  stats->kernel_ms = ms;
+  return hipSuccess;
 }
 
 hipError_t DeviceEngine::finish_deferred(LaunchStats* stats) {
@@ -721,578 +817,6 @@ hipError_t DeviceEngine::finish_deferred(LaunchStats* stats) {
   stats->kernel_ms = e == hipSuccess ? ms : 0.0;
   stats->defer = false;
   return e;
-}
-
-namespace {
-template <int T>
-int lazy_tiny_per_cu();
-}  // namespace
-
-hipError_t DeviceEngine::run_chain(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
-                                   int semantics, const BatchOutDev& out, hipStream_t stream,
-                                   LaunchStats* stats) {
-  HIP_TRY(hipSetDevice(dev_));
-  // the pull tiers alone copy paths out to the host (they must come first)
-  if (out.host_ol && !pull_first(rhs, semantics)) return hipErrorInvalidValue;
-  // host_w goes with host_ol: alone it would be BatchOutDev::text, which is launch_pull_part's
-  // (the streamed text batch) -- the tiers here read 4-B labels and emit no text
-  if (out.host_w && !out.host_ol) return hipErrorInvalidValue;
-  unsigned int* counter = (unsigned int*)scratch(kCounter, kCounterBytes);
-  if (!counter) return hipErrorOutOfMemory;
-  HIP_TRY(hipMemsetAsync(counter, 0, 64, stream));
-  HIP_TRY(hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), stream));
-  if (in.num_strings == 0) return hipSuccess;
-  // every string starts as INTERNAL: a string no kernel finished can never read as a result
-  // (after launch_pull_part the statuses are the pull tier's)
-  if (!after_pull_)
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out.status, kPathInternal, in.num_strings, stream));
-
-  // Eager semantics on a layered lattice -> eager-layered engine.
-  if (semantics == 1) {
-    if (rhs.nan) {  // NaN has no order in the reference's compare: UNSUPPORTED
-      mark_status_kernel<<<(in.num_strings + 255) / 256, 256, 0, stream>>>(in.num_strings, n,
-                                                                           rhs.view.start, out);
-      return hipGetLastError();
-    }
-    if (!rhs.nonneg) {
-      // Negative weights: shortest-path.zig's Dijkstra is then not the exact SSSP the
-      // parallel engines compute; the general engine builds each lattice and replays
-      // the heap order on it (sp_replay, kernels/eager_bfs.hpp).
-      if (stats) {
-        stats->engine = 6;
-        HIP_TRY(hipEventRecord(ev0_, stream));
-      }
-      HIP_TRY(run_bfs_chain(rhs, in, n, out, stream, true, false, true));
-      if (stats) {
-        HIP_TRY(hipEventRecord(ev1_, stream));
-        HIP_TRY(finish_stats(ev0_, ev1_, stats));
-      }
-      return hipSuccess;
-    }
-    if (rhs.has_eps) {  // not layered: the general BFS engine takes every string
-      if (stats) {
-        stats->engine = 2;
-        HIP_TRY(hipEventRecord(ev0_, stream));
-      }
-      HIP_TRY(run_bfs_chain(rhs, in, n, out, stream, true));
-      if (stats) {
-        HIP_TRY(hipEventRecord(ev1_, stream));
-        HIP_TRY(finish_stats(ev0_, ev1_, stats));
-      }
-      return hipSuccess;
-    }
-    // Tier chain for layered lattices (each tier takes the strings the previous one
-    // reports as OVERFLOW, through a device-side list):
-    //   P  one wavefront per string, pull over the reverse mirror, window of kPullW states
-    //      (when the rhs has one: DeviceFst::pull_ok)
-    //   A0 one wavefront per string, direct-mapped LDS window of kEwinW target states
-    //   A  one wavefront per string, LDS hash, <= kEwFcap tuples/layer, spans <= kEwKmax
-    //   B  256 threads per string, LDS tables, <= kElFcap tuples/layer, spans <= kElKmax
-    //   C  256 threads per string, HBM tables sized by the rhs (any layer)
-    // FSTAMD_EAGER_TIER1=window starts at A0, =wave at A, =wg at B (A/B comparisons).  A
-    // tier is skipped when the previous one provably cannot overflow on this rhs.
-    const char* t1 = std::getenv("FSTAMD_EAGER_TIER1");
-    const bool start_b = t1 && std::strcmp(t1, "wg") == 0;
-    const bool use_w = !start_b && !(t1 && std::strcmp(t1, "wave") == 0);
-    const bool use_p = use_w && rhs.pull_ok && !(t1 && std::strcmp(t1, "window") == 0);
-    const uint32_t ns = rhs.view.num_states, ms = rhs.view.max_span;
-    auto back_cap_for = [&](uint32_t fcap, uint64_t limit, bool* capped) {
-      const uint64_t want = (uint64_t)(in.max_len + 1) * fcap;
-      *capped = want > limit;
-      return (uint32_t)std::min<uint64_t>(want, limit);
-    };
-    bool cap_w = false, cap_a = false, cap_b = false;
-    const uint32_t back_cap_w = back_cap_for(kEwinW, 1u << 22, &cap_w);
-    const uint32_t back_cap_a = back_cap_for(kEwFcap, 1u << 22, &cap_a);
-    const uint32_t back_cap_b = back_cap_for(kElFcap, 1u << 22, &cap_b);
-    // A0 overflows on a window wider than kEwinW or an expanded layer of more than
-    // 64 * kEwinEmax tuples (both impossible with <= 64 * kEwinEmax states), on a span
-    // longer than kEwinKmax and on its back slab; only the first two are A's business.
-    const bool use_a = !start_b && (!use_w || ns > (uint32_t)(64 * kEwinEmax));
-    const bool need_b = !(use_w || use_a) || ns > (uint32_t)kEwFcap || ms > (uint32_t)kEwKmax ||
-                        (use_a && cap_a) || (use_w && (ms > (uint32_t)kEwinKmax || cap_w));
-    const bool need_c = need_b && (ns > (uint32_t)kElFcap || ms > (uint32_t)kElKmax || cap_b);
-    auto k_win = eager_window_kernel<kEwinEmax, kEwinRows, kEwinKmax, kEwinWaves>;
-    if (const char* ww = std::getenv("FSTAMD_EWIN_WAVES")) {  // occupancy experiments
-      if (std::strcmp(ww, "2") == 0) k_win = eager_window_kernel<kEwinEmax, kEwinRows, kEwinKmax, 2>;
-      if (std::strcmp(ww, "4") == 0) k_win = eager_window_kernel<kEwinEmax, kEwinRows, kEwinKmax, 4>;
-    }
-    auto k_wave = eager_wave_kernel<kEwFcap, kEwHcap, kEwEmax, kEwKmax>;
-    auto k_wg = eager_layered_lds_kernel<kElWG, kElFcap, kElHcap, kElKmax>;
-    auto grid_for = [&](const void* k, int block, uint32_t back_cap) -> uint32_t {
-      int occ = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, block, 0) != hipSuccess) occ = 1;
-      uint32_t g = (uint32_t)std::min<uint64_t>((uint64_t)std::max(occ, 1) * num_cus_,
-                                                in.num_strings);
-      while (g > 1 && (uint64_t)g * back_cap * sizeof(uint2) > (4ull << 30)) g /= 2;
-      return std::max<uint32_t>(g, 1);
-    };
-    // A0 keeps kChaseBatch back slabs per wave (backtraces are walked in batches)
-    uint32_t grid_w = 0;
-    if (use_w) {
-      int occ = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_win, 64, 0) !=
-          hipSuccess)
-        occ = 1;
-      grid_w = (uint32_t)std::min<uint64_t>((uint64_t)std::max(occ, 1) * num_cus_, in.num_strings);
-      // behind tier P, A0 only takes P's overflows: 2 waves per CU keep its slabs small
-      if (use_p) grid_w = std::min<uint32_t>(grid_w, 2u * (uint32_t)num_cus_);
-      while (grid_w > 1 && (uint64_t)grid_w * kChaseBatch * back_cap_w * 8 > (24ull << 30))
-        grid_w /= 2;
-      grid_w = std::max<uint32_t>(grid_w, 1);
-    }
-    // P: kChaseBatch back slabs per wave too, kPullW slots per layer
-    uint32_t grid_p = 0;
-    uint2* back_p = nullptr;
-    uint32_t* list_pw = nullptr;
-    if (use_p) {
-      grid_p = (uint32_t)std::min<uint64_t>((uint64_t)pull_waves_per_cu(rhs, in.max_len) * num_cus_,
-                                            in.num_strings);
-      grid_p = std::min<uint32_t>(grid_p, grid_cap("FSTAMD_P_GRID"));
-      while (grid_p > 1 && (uint64_t)grid_p * kChaseBatch * back_cap_w * 8 > (24ull << 30))
-        grid_p /= 2;
-      grid_p = std::max<uint32_t>(grid_p, 1);
-      back_p = (uint2*)scratch(kPullBack, (size_t)grid_p * kChaseBatch * back_cap_w * 8);
-      list_pw = (uint32_t*)scratch(kItems4, (size_t)in.num_strings * 4);
-      if (!back_p || !list_pw) return hipErrorOutOfMemory;
-    }
-    const uint32_t grid_a = use_a ? grid_for((const void*)k_wave, 64, back_cap_a) : 0;
-    const uint32_t grid_b = need_b ? grid_for((const void*)k_wg, kElWG, back_cap_b) : 0;
-    uint2* back_w =
-        use_w ? (uint2*)scratch(kElBackW, (size_t)grid_w * kChaseBatch * back_cap_w * 8) : nullptr;
-    uint2* back_a = use_a ? (uint2*)scratch(kElBack, (size_t)grid_a * back_cap_a * 8) : nullptr;
-    uint2* back_b = need_b ? (uint2*)scratch(kElBackB, (size_t)grid_b * back_cap_b * 8) : nullptr;
-    if ((use_w && !back_w) || (use_a && !back_a) || (need_b && !back_b))
-      return hipErrorOutOfMemory;
-    uint32_t* list_wa = (use_w && use_a) ? (uint32_t*)scratch(kItems3, (size_t)in.num_strings * 4)
-                                         : nullptr;
-    uint32_t* list_ab = ((use_w || use_a) && need_b)
-                            ? (uint32_t*)scratch(kItems, (size_t)in.num_strings * 4)
-                            : nullptr;
-    uint32_t* list_bc = need_c ? (uint32_t*)scratch(kItems2, (size_t)in.num_strings * 4) : nullptr;
-    if ((use_w && use_a && !list_wa) || ((use_w || use_a) && need_b && !list_ab) ||
-        (need_c && !list_bc))
-      return hipErrorOutOfMemory;
-    uint32_t grid_c = 0, fcap_c = 0, hcap_c = 0, back_cap_c = 0;
-    uint8_t* slab_c = nullptr;
-    uint2* back_c = nullptr;
-    if (need_c) {
-      fcap_c = std::max<uint32_t>(ns, 1);
-      hcap_c = next_pow2(2ull * fcap_c);
-      back_cap_c = (uint32_t)std::min<uint64_t>((uint64_t)(in.max_len + 1) * fcap_c, 1u << 28);
-      const uint64_t per_wg = layer_slab_bytes(fcap_c, hcap_c) + (uint64_t)back_cap_c * 8;
-      grid_c = (uint32_t)std::min<uint64_t>(num_cus_, std::max<uint64_t>(1, (8ull << 30) / per_wg));
-      slab_c = (uint8_t*)scratch(kElSlab, (size_t)grid_c * layer_slab_bytes(fcap_c, hcap_c));
-      back_c = (uint2*)scratch(kElBack2, (size_t)grid_c * back_cap_c * sizeof(uint2));
-      if (!slab_c || !back_c) return hipErrorOutOfMemory;
-    }
-    if (stats) {
-      stats->engine = 0;
-      stats->grid = use_p ? grid_p : use_w ? grid_w : use_a ? grid_a : grid_b;
-      stats->launches = (use_p ? 2 : 0) + (use_w ? 1 : 0) + (use_a ? (use_w ? 2 : 1) : 0) +
-                        (need_b ? ((use_w || use_a) ? 2 : 1) : 0) + (need_c ? 2 : 0);
-      HIP_TRY(hipEventRecord(ev0_, stream));
-    }
-    const unsigned long long wd = watchdog_ticks();
-    const uint32_t blocks = (in.num_strings + 255) / 256;
-    // counters: [14] item counter of tier P, [15] |list_pw|; [5] item counter of tier A0,
-    // [6] |list_wa|; [0..2] item counters of tiers A, B, C; [3] |list_ab|; [4] |list_bc|
-    if (use_p) {
-      EagerLaunch lp{nullptr, nullptr, in.num_strings, nullptr, 0, 0, back_p, back_cap_w, wd};
-      if (!after_pull_) HIP_TRY(launch_eager_pull(rhs, in, n, counter + 14, lp, out, grid_p, stream));
-      // test hook: FSTAMD_EAGER_ONLY_FIRST leaves tier P's OVERFLOW / UNSUPPORTED strings
-      // as they are, so a test can tell what the tier itself took
-      if (std::getenv("FSTAMD_EAGER_ONLY_FIRST")) {
-        if (stats) {
-          HIP_TRY(hipEventRecord(ev1_, stream));
-          HIP_TRY(finish_stats(ev0_, ev1_, stats));
-        }
-        return hipSuccess;
-      }
-    }
-    if (use_w) {
-      EagerLaunch lw{nullptr, nullptr, in.num_strings, nullptr, 0, 0, back_w, back_cap_w, wd};
-      if (use_p) {
-        collect_status_kernel<<<blocks, 256, 0, stream>>>(out.status, in.num_strings,
-                                                          kPathOverflow, list_pw, counter + 15);
-        lw.items = list_pw;
-        lw.num_items_dev = counter + 15;
-      }
-#ifdef FSTAMD_DEBUG_WAIT
-      HIP_TRY(debug_trace_arm());
-#endif
-      k_win<<<grid_w, 64, 0, stream>>>(rhs.view, in, n, counter + 5, lw, out);
-      HIP_TRY(hipGetLastError());
-#ifdef FSTAMD_DEBUG_WAIT
-      HIP_TRY(debug_wait(stream, grid_w, "tierA0"));
-#endif
-    }
-    if (use_a) {
-      EagerLaunch la{nullptr, nullptr, in.num_strings, nullptr, 0, 0, back_a, back_cap_a, wd};
-      if (use_w) {
-        collect_status_kernel<<<blocks, 256, 0, stream>>>(out.status, in.num_strings,
-                                                          kPathOverflow, list_wa, counter + 6);
-        la.items = list_wa;
-        la.num_items_dev = counter + 6;
-      }
-#ifdef FSTAMD_DEBUG_WAIT
-      HIP_TRY(debug_trace_arm());
-#endif
-      k_wave<<<grid_a, 64, 0, stream>>>(rhs.view, in, n, counter, la, out);
-      HIP_TRY(hipGetLastError());
-#ifdef FSTAMD_DEBUG_WAIT
-      HIP_TRY(debug_wait(stream, grid_a, "tierA"));
-#endif
-    }
-    if (need_b) {
-      EagerLaunch lb{nullptr, nullptr, in.num_strings, nullptr, 0, 0, back_b, back_cap_b, wd};
-      if (use_w || use_a) {
-        collect_status_kernel<<<blocks, 256, 0, stream>>>(out.status, in.num_strings,
-                                                          kPathOverflow, list_ab, counter + 3);
-        lb.items = list_ab;
-        lb.num_items_dev = counter + 3;
-      }
-      k_wg<<<grid_b, kElWG, 0, stream>>>(rhs.view, in, n, counter + 1, lb, out);
-      HIP_TRY(hipGetLastError());
-#ifdef FSTAMD_DEBUG_WAIT
-      HIP_TRY(debug_wait(stream, grid_b, "tierB"));
-#endif
-    }
-    if (need_c) {
-      collect_status_kernel<<<blocks, 256, 0, stream>>>(out.status, in.num_strings,
-                                                        kPathOverflow, list_bc, counter + 4);
-      EagerLaunch lc{list_bc, counter + 4, 0, slab_c, fcap_c, hcap_c, back_c, back_cap_c, wd};
-      eager_layered_kernel<kElWG, kElFcap, kElHcap, false>
-          <<<grid_c, kElWG, 0, stream>>>(rhs.view, in, n, counter + 2, lc, out);
-      HIP_TRY(hipGetLastError());
-#ifdef FSTAMD_DEBUG_WAIT
-      HIP_TRY(debug_wait(stream, grid_c, "tierC"));
-#endif
-    }
-    if (std::getenv("FSTAMD_ROUTE_LOG")) {  // how many strings each fallback tier took
-      unsigned int h[16] = {};
-      HIP_TRY(hipMemcpyAsync(h, counter, sizeof(h), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      std::fprintf(stderr,
-                   "[libfst_amd route] eager: %u strings, tiers P %d A0 %d A %d B %d C %d | "
-                   "handed on: P->A0 %u, A0->A %u, ->B %u, ->C %u\n",
-                   in.num_strings, (int)use_p, (int)use_w, (int)use_a, (int)need_b, (int)need_c,
-                   use_p && use_w ? h[15] : 0u, use_w && use_a ? h[6] : 0u,
-                   need_b && (use_w || use_a) ? h[3] : 0u, need_c ? h[4] : 0u);
-    }
-    // Strings the layered tiers cannot take (label-0 inputs -> UNSUPPORTED, tier-2
-    // OVERFLOW) go to the general BFS engine.
-    HIP_TRY(run_bfs_chain(rhs, in, n, out, stream, false));
-    if (stats) {
-      HIP_TRY(hipEventRecord(ev1_, stream));
-      HIP_TRY(finish_stats(ev0_, ev1_, stats));
-    }
-    return hipSuccess;
-  }
-
-  // Lazy semantics.  Finite weights >= 0 -> the parallel rounds engines or the dense
-  // replay; otherwise (+inf arcs, negative weights) the hashed exact replay.
-  //  * rhs without input epsilons: the layered rounds engine (kernels/lazy_layered.hpp),
-  //    then the general rounds engine (eager_bfs.hpp, bfs_lazy_path) for its leftovers;
-  //  * rhs with input epsilons: the dense replay (kernels/lazy_dense.hpp) -- on epsilon-
-  //    dense lattices nearly every tuple sits at one distance and the rounds degenerate to
-  //    one pop each -- with the general rounds engine for its leftovers.  Small lattices
-  //    too (config 4's tagger and verbalizer: 15.2 ms per two-stage call of 64K
-  //    utterances vs 18.4 ms in the hashed replay, whose per-wave tables live in HBM).
-  // FSTAMD_LAZY_ENGINE=rounds | replay | dense forces one engine (A/B runs, tests).
-  const char* le = std::getenv("FSTAMD_LAZY_ENGINE");
-  const bool force_rounds = le && std::strcmp(le, "rounds") == 0;
-  const bool force_replay = le && std::strcmp(le, "replay") == 0;
-  const bool force_dense = le && std::strcmp(le, "dense") == 0;
-  // "lds": the LDS replay first whatever the rhs (tests: rhs without input epsilons)
-  const bool force_lds = le && std::strcmp(le, "lds") == 0;
-  // The hashed replay (below) starts small lattices with its tables in LDS, then HBM for
-  // what outgrows them; FSTAMD_LAZY_TINY=0 skips that.  (As the engine for config 4's small
-  // epsilon lattices it measured level with the dense replay, 15.8 vs 15.0 ms per two-stage
-  // call: the pop's rhs reads and shuffles bind, not the tables.)
-  const char* lte = std::getenv("FSTAMD_LAZY_TINY");
-  const bool tiny_ok = !(lte && std::strcmp(lte, "0") == 0) &&
-                       (uint64_t)(in.max_len + 1) * rhs.view.num_states <= 16384;
-  const bool exact_ok = rhs.nonneg && rhs.finite && !force_replay;
-  const bool use_dense = exact_ok && !force_rounds && (force_dense || force_lds || rhs.has_eps);
-  const bool use_rounds = exact_ok && !use_dense;
-  if (use_dense) {
-    if (stats) {
-      stats->engine = 5;
-      stats->launches = 1;
-      HIP_TRY(hipEventRecord(ev0_, stream));
-    }
-    // Small lattices first, whatever the rhs size: the replay with the wave's tables in
-    // LDS at 128, then 256 tuples.  A WeText-scale tagger has 0.4 M states but ~140 tuples
-    // per utterance, while the dense replay's per-wave index is (L + 1) * NS * 2 tuples (1.6
-    // GB per wave there): it takes only what outgrows the LDS.  An rhs whose strings nearly
-    // all outgrow it (config 3's lattices of millions of tuples) skips the LDS pass from
-    // then on (DeviceFst::skip_tiny_lazy); FSTAMD_LAZY_TINY=0 skips it always.
-    const bool small = !force_dense && !(lte && std::strcmp(lte, "0") == 0) &&
-                       rhs.skip_tiny_lazy.load(std::memory_order_relaxed) == 0 &&
-                       in.num_strings > 0;
-    const uint32_t* todo = nullptr;  // the dense replay's strings (nullptr: all)
-    uint32_t todo_n = in.num_strings;
-    if (small) {
-      const uint32_t num = in.num_strings;
-      uint32_t* la = (uint32_t*)scratch(kItems, (size_t)num * 4);
-      uint32_t* lb = (uint32_t*)scratch(kItems2, (size_t)num * 4);
-      if (!la || !lb) return hipErrorOutOfMemory;
-      unsigned int* c = counter + 40;  // [40] items (LDS 128), [41] |la|, [42] items (256), [43] |lb|
-      HIP_TRY(hipMemsetAsync(c, 0, 16, stream));
-      uint32_t g = 0;
-      // the 128-tuple size first, unless it handed on over a third of an earlier batch on
-      // this rhs (DeviceFst::tiny_lazy_256: the WeText-scale tagger's lattices, 54 % over
-      // 128 tuples: tagger stage 46.7 -> 40.0 ms per 64 K utterances starting at 256);
-      // FSTAMD_LAZY_TINY_START=1|2 forces the first size
-      const char* ts = std::getenv("FSTAMD_LAZY_TINY_START");
-      const bool first128 = ts && *ts ? std::strcmp(ts, "2") != 0
-                                      : rhs.tiny_lazy_256.load(std::memory_order_relaxed) == 0;
-      uint32_t cnt[2] = {0, 0};
-      // A batch that the largest LDS size holds at once (coalesced single calls, small host
-      // batches) starts every string there: one wave per string whichever the size, so a
-      // long utterance no longer pays a replay at 256 tuples before its rerun at 512 or 1024
-      // (36 B per tuple: 1024 tuples are 38 KB, 4 waves per CU)
-      const bool direct = !(ts && *ts) &&
-                          (uint64_t)num <= (uint64_t)num_cus_ * lazy_tiny_per_cu<4>();
-      if (direct) {
-        HIP_TRY(run_lazy_tiny(rhs, in, n, out, stream, 4, nullptr, num, c + 2, &g));
-        if (stats) stats->grid = g;
-        collect_status_kernel<<<(num + 255) / 256, 256, 0, stream>>>(out.status, num,
-                                                                    kPathOverflow, lb, c + 3);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&cnt[1], c + 3, 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (num >= 64 && (uint64_t)cnt[1] * 10 > (uint64_t)num * 9)
-          rhs.skip_tiny_lazy.store(1, std::memory_order_relaxed);
-      } else if (first128) {
-        HIP_TRY(run_lazy_tiny(rhs, in, n, out, stream, 1, nullptr, num, c, &g));
-        if (stats) stats->grid = g;
-        collect_status_kernel<<<(num + 255) / 256, 256, 0, stream>>>(out.status, num,
-                                                                    kPathOverflow, la, c + 1);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&cnt[0], c + 1, 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-      } else {
-        cnt[0] = num;
-      }
-      if (!direct && cnt[0] > 0) {
-        HIP_TRY(run_lazy_tiny(rhs, in, n, out, stream, 2, first128 ? la : nullptr, cnt[0], c + 2, &g));
-        if (first128) {
-          collect_list_kernel<<<(cnt[0] + 255) / 256, 256, 0, stream>>>(la, c + 1, out.status,
-                                                                        kPathOverflow, lb, c + 3);
-        } else {
-          collect_status_kernel<<<(num + 255) / 256, 256, 0, stream>>>(out.status, num,
-                                                                      kPathOverflow, lb, c + 3);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&cnt[1], c + 3, 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (stats) stats->launches += 1;
-      }
-      if (!direct && first128 && num >= 1024 && (uint64_t)cnt[0] * 3 > (uint64_t)num)
-        rhs.tiny_lazy_256.store(1, std::memory_order_relaxed);
-      if (!direct && first128 && num < 1024) {  // small batches: the same rule over their sum
-        const uint64_t seen = rhs.tiny_lazy_seen.fetch_add(num) + num;
-        const uint64_t over = rhs.tiny_lazy_over.fetch_add(cnt[0]) + cnt[0];
-        if (seen >= 1024 && over * 3 > seen) rhs.tiny_lazy_256.store(1, std::memory_order_relaxed);
-      }
-      if (!direct && first128 && num >= 64 && (uint64_t)cnt[0] * 10 > (uint64_t)num * 9)
-        rhs.skip_tiny_lazy.store(1, std::memory_order_relaxed);
-      todo = lb;
-      todo_n = cnt[1];
-      uint32_t* rest = lb;             // the strings still OVERFLOW, and their count (device)
-      unsigned int* rest_cnt = c + 3;
-      uint32_t* spare = la;
-      unsigned int* spare_cnt = c + 1;
-      // Larger LDS sizes for the outliers of the LDS replays, or for every string of a small
-      // batch (a coalesced single call: a long utterance, ~400-900 tuples, went to the dense
-      // replay's HBM index -- 2.7 ms for 63 labels of the WeText-scale tagger): 512 tuples
-      // (~55 KB, 2 waves per CU), then 1024 (~110 KB, 1 per CU), one string per wave.
-      uint32_t cnt_big[2] = {0, 0};
-      for (int t = 3; !direct && t <= 4 && todo_n > 0 && ((uint64_t)todo_n * 4 <= num || num <= 64);
-           ++t) {
-        unsigned int* ci = counter + 48 + 2 * (t - 3);  // [48|50] items, [49|51] |next list|
-        HIP_TRY(hipMemsetAsync(ci, 0, 8, stream));
-        HIP_TRY(run_lazy_tiny(rhs, in, n, out, stream, t, rest, todo_n, ci, &g));
-        collect_list_kernel<<<(todo_n + 255) / 256, 256, 0, stream>>>(rest, rest_cnt, out.status,
-                                                                      kPathOverflow, spare, ci + 1);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&todo_n, ci + 1, 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        cnt_big[t - 3] = todo_n;
-        std::swap(rest, spare);
-        spare_cnt = rest_cnt;
-        rest_cnt = ci + 1;
-        todo = rest;
-        if (stats) stats->launches += 1;
-      }
-      // The LDS replays took most strings (>= 3/4): the rest are small-lattice outliers,
-      // served by the hashed replay (HBM tables sized by the lattice, x8 per retry) rather
-      // than by the dense index sized by (L + 1) * NS (a WeText-scale tagger: 1.6 GB per
-      // wave).  When they took few (large lattices), the dense replay takes the rest.
-      if (todo_n > 0 && (uint64_t)todo_n * 4 <= num) {
-        uint32_t* cur = rest;
-        unsigned int* cur_cnt = rest_cnt;
-        uint32_t* nxt = spare;
-        unsigned int* nxt_cnt = spare_cnt;
-        uint64_t want = 4096;
-        for (int t = 0; t < 4 && todo_n > 0; ++t, want *= 8) {
-          HIP_TRY(hipMemsetAsync(c + 4, 0, 4, stream));  // [44] item counter
-          if (launch_lazy_hashed(rhs, in, n, out, stream, want, cur, todo_n, c + 4, &g) !=
-              hipSuccess)
-            break;  // beyond its budget: the strings stay OVERFLOW for the dense replay
-          HIP_TRY(hipMemsetAsync(nxt_cnt, 0, 4, stream));
-          collect_list_kernel<<<(todo_n + 255) / 256, 256, 0, stream>>>(
-              cur, cur_cnt, out.status, kPathOverflow, nxt, nxt_cnt);
-          HIP_TRY(hipGetLastError());
-          HIP_TRY(hipMemcpyAsync(&todo_n, nxt_cnt, 4, hipMemcpyDeviceToHost, stream));
-          HIP_TRY(hipStreamSynchronize(stream));
-          std::swap(cur, nxt);
-          std::swap(cur_cnt, nxt_cnt);
-          if (stats) stats->launches += 1;
-        }
-        todo = cur;
-      }
-      if (std::getenv("FSTAMD_ROUTE_LOG"))
-        std::fprintf(stderr,
-                     "[libfst_amd route] lazy: %u strings, LDS-128 handed on %u, LDS-256 %u, "
-                     "LDS-512 %u, LDS-1024 %u, to the dense replay %u\n",
-                     num, cnt[0], cnt[1], cnt_big[0], cnt_big[1], todo_n);
-    }
-    // the LDS (and hashed) replays took every string: they leave none UNSUPPORTED, so there
-    // is nothing for the band, dense or general engines -- and the general engine's count
-    // readback would cost the call a synchronisation (the band and dense replays do mark
-    // strings UNSUPPORTED, so this holds only when neither runs)
-    const bool all_done = small && todo_n == 0;
-    bool ran = true;
-    if (todo_n > 0) {
-      // the band replay first (rhs whose arcs all go forward: config 3), the dense replay
-      // for what it hands on
-      // With the exact early exit a string only reaches ~2 L states past the start
-      // (config 3: DESIGN.md §4.2c), so the first launch keeps back pointers for a few
-      // windows of states; what reaches further runs again over the whole rhs.
-      const bool early_ok = rhs.nonneg && rhs.finite && !std::getenv("FSTAMD_NO_EARLY");
-      for (int pass = early_ok ? 0 : 1; pass < 2 && todo_n > 0; ++pass) {
-        bool band = false;
-        HIP_TRY(run_lazy_band(rhs, in, n, out, stream, &band, todo, todo ? todo_n : 0,
-                              pass == 0));
-        if (!band) break;
-        if (stats) stats->launches += 1;
-        // (the list `todo` may be kItems or kItems2: the next one goes elsewhere)
-        uint32_t* la = (uint32_t*)scratch(pass == 0 ? kItems3 : kItems4,
-                                          (size_t)in.num_strings * 4);
-        if (!la) return hipErrorOutOfMemory;
-        unsigned int* c = counter + 46;  // [46] |la|
-        HIP_TRY(hipMemsetAsync(c, 0, 4, stream));
-        collect_status_kernel<<<(in.num_strings + 255) / 256, 256, 0, stream>>>(
-            out.status, in.num_strings, kPathOverflow, la, c);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&todo_n, c, 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        todo = la;
-        if (std::getenv("FSTAMD_ROUTE_LOG"))
-          std::fprintf(stderr, "[libfst_amd route] lazy: band replay (%s) handed on %u\n",
-                       pass == 0 ? "capped, early exit" : "whole rhs", todo_n);
-      }
-    }
-    if (todo_n > 0) {
-      HIP_TRY(run_lazy_dense(rhs, in, n, out, stream, &ran, todo, todo ? todo_n : 0));
-      if (stats) stats->launches += 1;
-    }
-    if (stats && !ran) stats->engine = 3;  // too large for the dense engine: rounds only
-    if (!std::getenv("FSTAMD_DENSE_NOFALLBACK") && !all_done)  // debug: leave UNSUPPORTED
-      HIP_TRY(run_bfs_chain(rhs, in, n, out, stream, !ran && !small, true));
-    if (stats) {
-      HIP_TRY(hipEventRecord(ev1_, stream));
-      HIP_TRY(finish_stats(ev0_, ev1_, stats));
-    }
-    return hipSuccess;
-  }
-  if (use_rounds) {
-    if (stats) {
-      stats->engine = 3;
-      HIP_TRY(hipEventRecord(ev0_, stream));
-    }
-    // Layered lattices (no rhs input epsilon; label-0 inputs are sent on as UNSUPPORTED):
-    // the one-wave dense engine (kernels/lazy_layered.hpp), FSTAMD_LAZY_LAYERED=0 skips
-    // it; the general rounds engine takes everything else and its leftovers.
-    const char* ll = std::getenv("FSTAMD_LAZY_LAYERED");
-    const bool layered = !rhs.has_eps && rhs.view.max_span <= kLlSpanMax &&
-                         (uint64_t)(in.max_len + 1) * rhs.view.num_states <= kLlDenseMax &&
-                         !(ll && std::strcmp(ll, "0") == 0);
-    // Layer-local pull first (kernels/lazy_pull.hpp) when the rhs has a reverse mirror
-    // that suits it; the strings it hands on go to the rounds engines.
-    const bool use_lp = !rhs.has_eps && rhs.lazy_pull_ok && !force_rounds;
-    uint32_t* lp_list = nullptr;
-    uint32_t* lp_count = nullptr;
-    if (use_lp) {
-      if (stats) stats->engine = 7;
-      HIP_TRY(run_lazy_pull(rhs, in, n, out, stream, &lp_list, &lp_count, !after_pull_));
-      if (std::getenv("FSTAMD_LAZY_ONLY_FIRST")) {  // test hook: what the pull took alone
-        if (stats) {
-          HIP_TRY(hipEventRecord(ev1_, stream));
-          HIP_TRY(finish_stats(ev0_, ev1_, stats));
-        }
-        return hipSuccess;
-      }
-    }
-    if (layered) {
-      if (stats && !use_lp) stats->engine = 4;
-      HIP_TRY(run_lazy_layered(rhs, in, n, out, stream, lp_list, lp_count));
-    }
-    HIP_TRY(run_bfs_chain(rhs, in, n, out, stream, !layered && !use_lp, true));
-    if (stats) {
-      HIP_TRY(hipEventRecord(ev1_, stream));
-      HIP_TRY(finish_stats(ev0_, ev1_, stats));
-    }
-    return hipSuccess;
-  }
-  // Replay: the per-wave workspace is sized from max_len; strings that outgrow it
-  // (OVERFLOW) are re-run from a list with 8x the capacity and fewer waves, until they
-  // fit or the budget is exhausted.
-  auto launch_lazy = [&](uint64_t want_nodes, const uint32_t* items, uint32_t num_items,
-                         unsigned int* ctr, uint32_t* grid_out) -> hipError_t {
-    return launch_lazy_hashed(rhs, in, n, out, stream, want_nodes, items, num_items, ctr,
-                              grid_out);
-  };
-  uint64_t want = std::max<uint64_t>(4096, (uint64_t)256 * (in.max_len + 1));
-  if (stats) {
-    stats->engine = 1;
-    stats->launches = 1;
-    HIP_TRY(hipEventRecord(ev0_, stream));
-  }
-  uint32_t grid0 = 0;
-  const bool tiny_first = tiny_ok;
-  if (tiny_first) {  // LDS tables (kernels/lazy_wave.hpp, 128 tuples)
-    HIP_TRY(run_lazy_tiny(rhs, in, n, out, stream, 1, nullptr, in.num_strings, counter, &grid0));
-  } else {
-    HIP_TRY(launch_lazy(want, nullptr, in.num_strings, counter, &grid0));
-  }
-  if (stats) stats->grid = grid0;
-  // retry tiers for OVERFLOW strings (host reads the count: this path is for outliers)
-  uint32_t* list = (uint32_t*)scratch(kItems, (size_t)in.num_strings * 4);
-  if (!list) return hipErrorOutOfMemory;
-  for (int tier = 1; tier <= 4; ++tier) {
-    unsigned int* ctr = counter + 4 + 2 * tier;  // [item counter, list count] per tier
-    HIP_TRY(hipMemsetAsync(ctr, 0, 8, stream));
-    collect_status_kernel<<<(in.num_strings + 255) / 256, 256, 0, stream>>>(
-        out.status, in.num_strings, kPathOverflow, list, ctr + 1);
-    HIP_TRY(hipGetLastError());
-    uint32_t cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, ctr + 1, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (cnt == 0) break;
-    if (!(tiny_first && tier == 1)) want *= 8;  // after the tiny launch: HBM at `want` first
-    uint32_t g = 0;
-    if (launch_lazy(want, list, cnt, ctr, &g) != hipSuccess) break;  // stays OVERFLOW
-    if (stats) stats->launches += 2;
-  }
-  if (stats) {
-    HIP_TRY(hipEventRecord(ev1_, stream));
-    HIP_TRY(finish_stats(ev0_, ev1_, stats));
-  }
-  return hipSuccess;
 }
 
 // ---------------------------------------------------------------------------------
@@ -1326,25 +850,12 @@ BfsCaps bfs_caps(int tier) {
 }
 }  // namespace
 
-__global__ void collect_status2_kernel(const int32_t* status, uint32_t num, int32_t a, int32_t b,
-                                       uint32_t* list, uint32_t* count) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < num && (status[i] == a || status[i] == b)) list[atomicAdd(count, 1u)] = i;
-}
-
-__global__ void collect_list_kernel(const uint32_t* in_list, const uint32_t* in_count,
-                                    const int32_t* status, int32_t code, uint32_t* list,
-                                    uint32_t* count) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < *in_count && status[in_list[i]] == code) list[atomicAdd(count, 1u)] = in_list[i];
-}
-
 // One-wave dense lazy engine for layered lattices.  Its per-wave dense arrays are left
 // clean by every string, so they are initialised only when (re)allocated.
 hipError_t DeviceEngine::run_lazy_pull(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
                                        const BatchOutDev& out, hipStream_t stream,
                                        uint32_t** list, uint32_t** count_dev, bool launch) {
-  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);  // [34..35] are ours
+  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);
   if (!ctr) return hipErrorOutOfMemory;
   // kChaseBatch back slabs per wave, kPullW slots per layer (as tier P)
   const uint32_t back_cap =
@@ -1357,14 +868,13 @@ hipError_t DeviceEngine::run_lazy_pull(const DeviceFst& rhs, const ChainInput& i
   uint2* back = (uint2*)scratch(kLpBack, (size_t)grid * kChaseBatch * back_cap * 8);
   uint32_t* lst = (uint32_t*)scratch(kItems5, (size_t)in.num_strings * 4);
   if (!back || !lst) return hipErrorOutOfMemory;
-  HIP_TRY(hipMemsetAsync(ctr + 34, 0, 8, stream));
+  HIP_TRY(hipMemsetAsync(ctr + kCtrLazyPullItem, 0, 8, stream));
   EagerLaunch lp{nullptr, nullptr, in.num_strings, nullptr, 0, 0, back, back_cap, watchdog_ticks()};
-  if (launch) HIP_TRY(launch_lazy_pull(rhs, in, n, ctr + 34, lp, out, grid, stream));
-  collect_status_kernel<<<(in.num_strings + 255) / 256, 256, 0, stream>>>(
-      out.status, in.num_strings, kPathOverflow, lst, ctr + 35);
-  HIP_TRY(hipGetLastError());
+  if (launch) HIP_TRY(launch_lazy_pull(rhs, in, n, ctr + kCtrLazyPullItem, lp, out, grid, stream));
+  // (no read-back: the layered engine takes the list on the device)
+  HIP_TRY(collect(with_status(in.num_strings), out.status, lst, ctr + kCtrLazyPullList, stream));
   *list = lst;
-  *count_dev = ctr + 35;
+  *count_dev = ctr + kCtrLazyPullList;
   return hipSuccess;
 }
 
@@ -1415,7 +925,7 @@ hipError_t DeviceEngine::run_lazy_layered(const DeviceFst& rhs, const ChainInput
                                           uint32_t n, const BatchOutDev& out,
                                           hipStream_t stream, const uint32_t* items,
                                           const uint32_t* num_items_dev) {
-  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);  // [32] is ours
+  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);
   if (!ctr) return hipErrorOutOfMemory;
   LlWs ws{};
   ws.lcap = in.max_len;
@@ -1453,11 +963,11 @@ hipError_t DeviceEngine::run_lazy_layered(const DeviceFst& rhs, const ChainInput
     ll_clean_ = bufs_[kLlDk];
     ll_clean_bytes_ = sizes_[kLlDk];
   }
-  HIP_TRY(hipMemsetAsync(ctr + 32, 0, 4, stream));
+  HIP_TRY(hipMemsetAsync(ctr + kCtrLayeredItem, 0, 4, stream));
   const bool prof = std::getenv("FSTAMD_BFS_PROF") != nullptr;
   ws.prof = prof ? (unsigned long long*)scratch(kDebug, g * 64) : nullptr;
   if (ws.prof) HIP_TRY(hipMemsetAsync(ws.prof, 0, g * 64, stream));
-  lazy_layered_kernel<<<grid, 64, 0, stream>>>(rhs.view, in, n, ctr + 32, ws, out);
+  lazy_layered_kernel<<<grid, 64, 0, stream>>>(rhs.view, in, n, ctr + kCtrLayeredItem, ws, out);
   HIP_TRY(hipGetLastError());
   if (ws.prof) {  // phase profile: sums over waves, ticks at 100 MHz
     std::vector<unsigned long long> h(g * 8);
@@ -1542,23 +1052,13 @@ hipError_t DeviceEngine::launch_lazy_hashed(const DeviceFst& rhs, const ChainInp
 }
 
 namespace {
-template <int T>
-int lazy_tiny_per_cu() {  // resident LDS-replay waves per CU, asked of the runtime once
+// resident one-wave workgroups per CU of a kernel whose tables sit in LDS (the LDS replays,
+// the ladder's tiny tiers), asked of the runtime once per kernel
+template <auto K>
+int waves_per_cu() {
   static const int occ = [] {
     int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &o, (const void*)lazy_tiny_kernel<T>, 64, 0) != hipSuccess)
-      o = 1;
-    return std::max(o, 1);
-  }();
-  return occ;
-}
-template <int N>
-int ctiny_per_cu() {
-  static const int occ = [] {
-    int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)eager_tiny_kernel<N>, 64,
-                                                     0) != hipSuccess)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, (const void*)K, 64, 0) != hipSuccess)
       o = 1;
     return std::max(o, 1);
   }();
@@ -1580,8 +1080,10 @@ hipError_t DeviceEngine::run_lazy_tiny(const DeviceFst& rhs, const ChainInput& i
   ws.stamp_base = eg ? (uint32_t)std::strtoul(eg, nullptr, 10) & 0xFFFFu : 0u;
   const uint32_t cap_waves = ew ? (uint32_t)std::strtoul(ew, nullptr, 10) : 0u;
   ws.wd_ticks = watchdog_ticks();
-  const int occ = tier == 1 ? lazy_tiny_per_cu<1>() : tier == 2 ? lazy_tiny_per_cu<2>()
-                 : tier == 3 ? lazy_tiny_per_cu<3>() : lazy_tiny_per_cu<4>();
+  const int occ = tier == 1   ? waves_per_cu<lazy_tiny_kernel<1>>()
+                  : tier == 2 ? waves_per_cu<lazy_tiny_kernel<2>>()
+                  : tier == 3 ? waves_per_cu<lazy_tiny_kernel<3>>()
+                              : waves_per_cu<lazy_tiny_kernel<4>>();
   uint32_t grid =
       (uint32_t)std::min<uint64_t>((uint64_t)num_cus_ * occ, std::max(num_items, 1u));
   if (cap_waves) grid = std::min(grid, cap_waves);
@@ -1627,7 +1129,7 @@ hipError_t DeviceEngine::run_lazy_band(const DeviceFst& rhs, const ChainInput& i
   *ran = false;
   if (rhs.view.jump_back != 0 || std::getenv("FSTAMD_NO_BAND")) return hipSuccess;
   if (rhs.view.start >= rhs.view.num_states) capped = false;  // (no start: all EMPTY)
-  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);  // [36] is ours
+  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);
   if (!ctr) return hipErrorOutOfMemory;
   // the strings and their lengths on the host (plans, buckets, longest first)
   std::vector<uint64_t> off((size_t)in.num_strings + 1);
@@ -1784,7 +1286,7 @@ hipError_t DeviceEngine::run_lazy_band(const DeviceFst& rhs, const ChainInput& i
     ws.wd_tuple_ticks = std::getenv("FSTAMD_WATCHDOG_MS") ? 0ull : 1000ull;
     ws.items = d_order + p.first;
     ws.num_items = p.count;
-    HIP_TRY(hipMemsetAsync(ctr + 36, 0, 4, stream));
+    HIP_TRY(hipMemsetAsync(ctr + kCtrBandItem, 0, 4, stream));
     // back pointers of 1, 2 or 4 B: one instance each
     // (and the slot path's preconditions as a compile-time fact when they hold)
     // (the slot fold also needs the arcs in (ilabel, olabel) order: an rhs without it takes
@@ -1797,7 +1299,7 @@ hipError_t DeviceEngine::run_lazy_band(const DeviceFst& rhs, const ChainInput& i
     if (p.lds > 64 * 1024)
       HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)p.lds));
-    kern<<<p.grid, 64, p.lds, stream>>>(rhs.view, in, n, ctr + 36, ws, out);
+    kern<<<p.grid, 64, p.lds, stream>>>(rhs.view, in, n, ctr + kCtrBandItem, ws, out);
     HIP_TRY(hipGetLastError());
   }
   *ran = true;
@@ -1888,7 +1390,7 @@ hipError_t DeviceEngine::run_lazy_dense(const DeviceFst& rhs, const ChainInput& 
       return hipSuccess;
     }
   }
-  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);  // [33] is ours
+  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);
   if (!ctr) return hipErrorOutOfMemory;
   // One launch plan: the per-wave dense state is sized by the longest string it takes.
   struct Plan {
@@ -2054,14 +1556,14 @@ hipError_t DeviceEngine::run_lazy_dense(const DeviceFst& rhs, const ChainInput& 
     ws.wd_tuple_ticks = std::getenv("FSTAMD_WATCHDOG_MS") ? 0ull : 1000ull;
     ws.items = d_order ? d_order + p.first : nullptr;
     ws.num_items = p.count;
-    HIP_TRY(hipMemsetAsync(ctr + 33, 0, 4, stream));
+    HIP_TRY(hipMemsetAsync(ctr + kCtrDenseItem, 0, 4, stream));
 #ifdef FSTAMD_DEBUG_WAIT
     HIP_TRY(debug_trace_arm());
 #endif
     if (p.lds > 64 * 1024)  // beyond the default dynamic-LDS limit of a launch
       HIP_TRY(hipFuncSetAttribute((const void*)lazy_dense_kernel,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-    lazy_dense_kernel<<<p.grid, 64, p.lds, stream>>>(rhs.view, in, n, ctr + 33, ws, out);
+    lazy_dense_kernel<<<p.grid, 64, p.lds, stream>>>(rhs.view, in, n, ctr + kCtrDenseItem, ws, out);
     HIP_TRY(hipGetLastError());
 #ifdef FSTAMD_DEBUG_WAIT
     HIP_TRY(debug_wait(stream, p.grid, "lazy_dense"));
@@ -2097,82 +1599,35 @@ hipError_t DeviceEngine::run_lazy_dense(const DeviceFst& rhs, const ChainInput& 
   return hipSuccess;
 }
 
-namespace {
-// resident tiny-tier workgroups per CU (LDS-bound), asked of the runtime once per size
-template <int K>
-int tiny_per_cu() {
-  static const int occ = [] {
-    int o = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &o, (const void*)eager_bfs_kernel<64, false, K>, 64, 0) != hipSuccess)
-      o = 1;
-    return std::max(o, 1);
-  }();
-  return occ;
-}
-}  // namespace
-
-hipError_t DeviceEngine::run_bfs_chain(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
-                                       const BatchOutDev& out, hipStream_t stream, bool all,
-                                       bool lazy, bool replay) {
-  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);  // [8..15] are ours
-  uint32_t* list = (uint32_t*)scratch(kBfsList, (size_t)in.num_strings * 4);
-  uint32_t* list2 = (uint32_t*)scratch(kBfsList2, (size_t)in.num_strings * 4);
-  if (!ctr || !list || !list2) return hipErrorOutOfMemory;
-  uint32_t* cnt = ctr + 8;
-  HIP_TRY(hipMemsetAsync(cnt, 0, 32, stream));
-  const uint32_t blocks = (in.num_strings + 255) / 256;
-  if (all) {
-    mark_status_kernel<<<blocks, 256, 0, stream>>>(in.num_strings, 1, rhs.view.start, out);
-    collect_status2_kernel<<<blocks, 256, 0, stream>>>(out.status, in.num_strings,
-                                                       kPathUnsupported, kPathUnsupported, list,
-                                                       cnt);
-  } else {
-    collect_status2_kernel<<<blocks, 256, 0, stream>>>(out.status, in.num_strings,
-                                                       kPathUnsupported, kPathOverflow, list, cnt);
-  }
-  HIP_TRY(hipGetLastError());
-  uint32_t count = 0;
-  HIP_TRY(hipMemcpyAsync(&count, cnt, 4, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  // Tiers -2 and -1 (tiny, tables in LDS, kernels/eager_bfs.hpp tiny_caps) first when the lattices are
-  // small by the product bound; not for the exact heap replay (negative weights), whose
-  // heap lives in HBM.  FSTAMD_BFS_TINY=0 turns it off (A/B runs, tests).
+// The tier ladder of the general BFS engine, shared by run_bfs_chain, run_lhs_eager and
+// run_lattice_batch: `list` holds `count` items and cnt[0] = count on the device; cnt[1] is
+// the item counter, cnt[2] the next list's count.  Tiers -2 / -1 keep their tables in LDS
+// (128 / 256 tuples), tier 0 is the first HBM size, every later tier holds x8; what a tier
+// leaves OVERFLOW moves to the next.  L.launch queues one tier's kernel; L.per_cu gives an
+// LDS tier's resident workgroups per CU.  FSTAMD_BFS_TINY=0 turns the LDS tiers off.
+hipError_t DeviceEngine::run_bfs_ladder(uint32_t count, uint32_t* list, uint32_t* list2,
+                                        uint32_t* cnt, const int32_t* status,
+                                        const BfsLadder& L, hipStream_t stream, LhsRoute* route,
+                                        uint32_t* grid_out) {
   const char* te = std::getenv("FSTAMD_BFS_TINY");
-  // Small lattices by the product bound always fit; beyond it the tiny tiers are tried too
-  // (a WeText-scale rhs: 0.4 M states, ~140 tuples per utterance) unless an earlier batch
-  // on this rhs handed nearly every string on (DeviceFst::skip_tiny_eager).
-  const bool tiny = !replay && !(te && std::strcmp(te, "0") == 0) &&
-                    ((uint64_t)(in.max_len + 1) * rhs.view.num_states <= 16384 ||
-                     rhs.skip_tiny_eager.load(std::memory_order_relaxed) == 0);
-  const uint32_t count0 = count;
-  // Eager semantics on an rhs a one-word tuple key can name: the compact tiny tiers
-  // (kernels/eager_tiny.hpp, ~52 B per tuple instead of ~110: 23 / 12 workgroups per CU
-  // instead of 10 / 5).  FSTAMD_EAGER_CTINY=0 keeps eager_bfs_kernel's (A/B runs, tests).
-  const char* cte = std::getenv("FSTAMD_EAGER_CTINY");
-  const bool compact = tiny && !lazy && !(cte && std::strcmp(cte, "0") == 0) &&
-                       rhs.view.num_states < kCtMaxStates && rhs.view.num_arcs < kCtPhase3;
-  // tier -2: the 128-tuple tiny size, tier -1: the 256-tuple one, then the HBM tiers.
-  // The 128-tuple size is skipped on an rhs where it handed on over a third of an earlier
-  // batch (DeviceFst::tiny_eager_256); FSTAMD_BFS_TINY_START=1|2 forces the first size.
-  const char* tse = std::getenv("FSTAMD_BFS_TINY_START");
-  const bool first128 = tse && *tse ? std::strcmp(tse, "2") != 0
-                                    : rhs.tiny_eager_256.load(std::memory_order_relaxed) == 0;
-  for (int tier = tiny ? (first128 ? -2 : -1) : 0; count > 0; ++tier) {
+  const bool tiny = L.first < 0 && !(te && std::strcmp(te, "0") == 0);
+  for (int tier = tiny ? L.first : 0; count > 0; ++tier) {
     const TinyCaps tc = tiny_caps(tier == -2 ? 1 : 2);
     const BfsCaps c = tier < 0 ? BfsCaps{tc.n, tc.a, tc.h, tc.l, 0} : bfs_caps(tier);
     const uint64_t fit = tier < 0 ? ~0ull : std::max<uint64_t>(1, kBfsBudget / c.stride);
-    if (kBfsBudget < c.stride) break;  // beyond the budget: those strings stay OVERFLOW
-    // tier 0: small lattices -> one wavefront per string by default (wave-level
-    // barriers, 4x the strings in flight); FSTAMD_BFS_WG0=256 for A/B runs
-    const char* wge = std::getenv("FSTAMD_BFS_WG0");
-    const bool wave = tier == 0 && !(wge && std::strcmp(wge, "256") == 0);
-    const uint64_t per_cu = tier < 0 ? (uint64_t)(compact ? (tier == -2 ? ctiny_per_cu<128>()
-                                                                        : ctiny_per_cu<256>())
-                                                 : tier == -2 ? tiny_per_cu<1>() : tiny_per_cu<2>())
-                            : tier == 0 ? (wave ? 4 * FSTAMD_BFS_WAVES64 : kBfsWgPerCu0) : 1;
-    const uint32_t grid =
-        (uint32_t)std::min<uint64_t>({(uint64_t)count, (uint64_t)num_cus_ * per_cu, fit});
+    if (kBfsBudget < c.stride) break;  // beyond the budget: those items stay OVERFLOW
+    // tier 0: small lattices -> one wavefront per item by default (wave-level barriers, 4x
+    // the items in flight)
+    const bool wave = tier == 0 && !L.wg0;
+    const int kind = tier == -2 ? kLhsTierTiny128
+                     : tier == -1 ? kLhsTierTiny256
+                     : wave ? kLhsTierWave
+                            : kLhsTierWG;
+    const uint64_t per_cu = tier < 0 ? (uint64_t)L.per_cu(kind)
+                            : tier == 0 ? (wave ? 4 * FSTAMD_BFS_WAVES64 : kBfsWgPerCu0)
+                                        : 1;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(
+        {(uint64_t)count, (uint64_t)num_cus_ * per_cu, fit, (uint64_t)L.grid_cap});
     BfsWs ws{};
     ws.slab = tier < 0 ? nullptr : (uint8_t*)scratch(kBfsSlab, (size_t)grid * c.stride);
     ws.hdr = (uint32_t*)scratch(kBfsHdr, (size_t)grid * 8 * 4);
@@ -2183,38 +1638,17 @@ hipError_t DeviceEngine::run_bfs_chain(const DeviceFst& rhs, const ChainInput& i
     ws.hcap = c.hcap;
     ws.lcap = c.lcap;
     ws.wd_ticks = watchdog_ticks();
-    ws.lattice_only = 0;
-    ws.lazy = lazy ? 1u : 0u;
-    if (replay && !lazy) {  // heap + settled flags per workgroup (kernels/eager_bfs.hpp)
-      ws.replay = (uint8_t*)scratch(kBfsHeap,
-                                    (size_t)grid * ((size_t)(c.acap + 1) * 16 + c.ncap));
+    ws.lattice_only = L.lattice_only;
+    ws.lazy = L.lazy ? 1u : 0u;
+    if (L.replay) {  // heap + settled flags per workgroup (kernels/eager_bfs.hpp)
+      ws.replay =
+          (uint8_t*)scratch(kBfsHeap, (size_t)grid * ((size_t)(c.acap + 1) * 16 + c.ncap));
       if (!ws.replay) return hipErrorOutOfMemory;
     }
-    const bool prof = std::getenv("FSTAMD_BFS_PROF") != nullptr;
-    ws.prof = prof ? (unsigned long long*)scratch(kDebug, (size_t)grid * 64) : nullptr;
+    ws.prof = L.prof ? (unsigned long long*)scratch(kDebug, (size_t)grid * 64) : nullptr;
     if (ws.prof) HIP_TRY(hipMemsetAsync(ws.prof, 0, (size_t)grid * 64, stream));
     HIP_TRY(hipMemsetAsync(cnt + 1, 0, 8, stream));  // item counter + next list count
-    GraphInput none{};
-    if (tier < 0 && compact) {
-      if (tier == -2)
-        eager_tiny_kernel<128><<<grid, 64, 0, stream>>>(rhs.view, in, n, cnt + 1, list, cnt,
-                                                        ws.wd_ticks, out);
-      else
-        eager_tiny_kernel<256><<<grid, 64, 0, stream>>>(rhs.view, in, n, cnt + 1, list, cnt,
-                                                        ws.wd_ticks, out);
-    } else if (tier == -2)
-      eager_bfs_kernel<64, false, 1><<<grid, 64, 0, stream>>>(rhs.view, in, none, n, cnt + 1,
-                                                              list, cnt, 0, ws, out);
-    else if (tier == -1)
-      eager_bfs_kernel<64, false, 2><<<grid, 64, 0, stream>>>(rhs.view, in, none, n, cnt + 1,
-                                                              list, cnt, 0, ws, out);
-    else if (wave)
-      eager_bfs_kernel<64, false><<<grid, 64, 0, stream>>>(rhs.view, in, none, n, cnt + 1, list,
-                                                           cnt, 0, ws, out);
-    else
-      eager_bfs_kernel<kBfsWG, false><<<grid, kBfsWG, 0, stream>>>(rhs.view, in, none, n, cnt + 1,
-                                                                   list, cnt, 0, ws, out);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(L.launch(kind, ws, cnt + 1, list, cnt, grid));
     if (ws.prof) {  // phase profile: sums over workgroups, ticks at 100 MHz
       std::vector<unsigned long long> h((size_t)grid * 8);
       HIP_TRY(hipMemcpyAsync(h.data(), ws.prof, h.size() * 8, hipMemcpyDeviceToHost, stream));
@@ -2230,22 +1664,666 @@ hipError_t DeviceEngine::run_bfs_chain(const DeviceFst& rhs, const ChainInput& i
                    (double)sum[5] / sum[4], (double)sum[6] / std::max(1ull, sum[5]),
                    (double)sum[7] / std::max(1ull, sum[5]));
     }
-    // strings that overflowed this tier move on to the next one
-    collect_list_kernel<<<(count + 255) / 256, 256, 0, stream>>>(list, cnt, out.status,
-                                                                 kPathOverflow, list2, cnt + 2);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&count, cnt + 2, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(cnt, cnt + 2, 4, hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    if (route) {
+      route->t[std::min(tier + 2, 3)] += count;
+      route->tiers_run += 1;
+    }
+    if (grid_out) *grid_out = std::max(*grid_out, grid);
+    // items that overflowed this tier move on to the next one
+    const uint32_t count_in = count;
+    HIP_TRY(hand_on(from_list(list, cnt, count_in), status, list2, cnt + 2, &count, stream, cnt));
     std::swap(list, list2);
-    if (tier == -2 && count0 >= 1024 && (uint64_t)count * 3 > (uint64_t)count0)
-      rhs.tiny_eager_256.store(1, std::memory_order_relaxed);
-    // the 128-tuple tier handed on nearly every string: skip the tiny tiers on this rhs
-    if (tier == -2 && count0 >= 64 && (uint64_t)count * 10 > (uint64_t)count0 * 9 &&
-        (uint64_t)(in.max_len + 1) * rhs.view.num_states > 16384)
-      rhs.skip_tiny_eager.store(1, std::memory_order_relaxed);
+    if (L.after) L.after(tier, count_in, count);
   }
   return hipSuccess;
+}
+
+hipError_t DeviceEngine::run_bfs_chain(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
+                                       const BatchOutDev& out, hipStream_t stream, bool all,
+                                       bool lazy, bool replay) {
+  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);
+  uint32_t* list = (uint32_t*)scratch(kBfsList, (size_t)in.num_strings * 4);
+  uint32_t* list2 = (uint32_t*)scratch(kBfsList2, (size_t)in.num_strings * 4);
+  if (!ctr || !list || !list2) return hipErrorOutOfMemory;
+  uint32_t* cnt = ctr + kCtrBfsCount;
+  HIP_TRY(hipMemsetAsync(cnt, 0, kCtrBfsWords * 4, stream));
+  const uint32_t num = in.num_strings;
+  if (all)
+    mark_status_kernel<<<(num + 255) / 256, 256, 0, stream>>>(num, 1, rhs.view.start, out);
+  uint32_t count = 0;
+  HIP_TRY(hand_on(with_status2(num, kPathUnsupported, all ? kPathUnsupported : kPathOverflow),
+                  out.status, list, cnt, &count, stream));
+  // Tiers -2 and -1 (tiny, tables in LDS, kernels/eager_bfs.hpp tiny_caps) first when the lattices are
+  // small by the product bound; not for the exact heap replay (negative weights), whose
+  // heap lives in HBM.  FSTAMD_BFS_TINY=0 turns it off (A/B runs, tests).
+  const char* te = std::getenv("FSTAMD_BFS_TINY");
+  // Small lattices by the product bound always fit; beyond it the tiny tiers are tried too
+  // (a WeText-scale rhs: 0.4 M states, ~140 tuples per utterance) unless an earlier batch
+  // on this rhs handed nearly every string on (DeviceFst::skip_tiny_eager).
+  const bool small = (uint64_t)(in.max_len + 1) * rhs.view.num_states <= 16384;
+  const bool tiny = !replay && !(te && std::strcmp(te, "0") == 0) &&
+                    (small || rhs.skip_tiny_eager.load(std::memory_order_relaxed) == 0);
+  const uint32_t count0 = count;
+  // Eager semantics on an rhs a one-word tuple key can name: the compact tiny tiers
+  // (kernels/eager_tiny.hpp, ~52 B per tuple instead of ~110: 23 / 12 workgroups per CU
+  // instead of 10 / 5).  FSTAMD_EAGER_CTINY=0 keeps eager_bfs_kernel's (A/B runs, tests).
+  const char* cte = std::getenv("FSTAMD_EAGER_CTINY");
+  const bool compact = tiny && !lazy && !(cte && std::strcmp(cte, "0") == 0) &&
+                       rhs.view.num_states < kCtMaxStates && rhs.view.num_arcs < kCtPhase3;
+  // tier -2: the 128-tuple tiny size, tier -1: the 256-tuple one, then the HBM tiers.
+  // The 128-tuple size is skipped on an rhs where it handed on over a third of an earlier
+  // batch (DeviceFst::tiny_eager_256); FSTAMD_BFS_TINY_START=1|2 forces the first size.
+  const char* tse = std::getenv("FSTAMD_BFS_TINY_START");
+  const bool first128 = tse && *tse ? std::strcmp(tse, "2") != 0
+                                    : rhs.tiny_eager_256.load(std::memory_order_relaxed) == 0;
+  const char* wge = std::getenv("FSTAMD_BFS_WG0");  // tier 0 with 256 threads, for A/B runs
+  BfsLadder L;
+  L.first = tiny ? (first128 ? -2 : -1) : 0;
+  L.replay = replay && !lazy;
+  L.lazy = lazy;
+  L.wg0 = wge && std::strcmp(wge, "256") == 0;
+  L.prof = std::getenv("FSTAMD_BFS_PROF") != nullptr;
+  L.per_cu = [compact](int kind) {
+    const bool k128 = kind == kLhsTierTiny128;
+    if (compact)
+      return k128 ? waves_per_cu<eager_tiny_kernel<128>>() : waves_per_cu<eager_tiny_kernel<256>>();
+    return k128 ? waves_per_cu<eager_bfs_kernel<64, false, 1>>()
+                : waves_per_cu<eager_bfs_kernel<64, false, 2>>();
+  };
+  L.launch = [&](int kind, const BfsWs& ws, unsigned int* next_item, const uint32_t* cur,
+                 const uint32_t* cur_count, uint32_t grid) {
+    const GraphInput none{};
+    if (kind == kLhsTierTiny128 && compact)
+      eager_tiny_kernel<128><<<grid, 64, 0, stream>>>(rhs.view, in, n, next_item, cur, cur_count,
+                                                      ws.wd_ticks, out);
+    else if (kind == kLhsTierTiny256 && compact)
+      eager_tiny_kernel<256><<<grid, 64, 0, stream>>>(rhs.view, in, n, next_item, cur, cur_count,
+                                                      ws.wd_ticks, out);
+    else if (kind == kLhsTierTiny128)
+      eager_bfs_kernel<64, false, 1><<<grid, 64, 0, stream>>>(rhs.view, in, none, n, next_item,
+                                                              cur, cur_count, 0, ws, out);
+    else if (kind == kLhsTierTiny256)
+      eager_bfs_kernel<64, false, 2><<<grid, 64, 0, stream>>>(rhs.view, in, none, n, next_item,
+                                                              cur, cur_count, 0, ws, out);
+    else if (kind == kLhsTierWave)
+      eager_bfs_kernel<64, false><<<grid, 64, 0, stream>>>(rhs.view, in, none, n, next_item, cur,
+                                                           cur_count, 0, ws, out);
+    else
+      eager_bfs_kernel<kBfsWG, false><<<grid, kBfsWG, 0, stream>>>(rhs.view, in, none, n,
+                                                                   next_item, cur, cur_count, 0,
+                                                                   ws, out);
+    return hipGetLastError();
+  };
+  L.after = [&rhs, count0, small](int tier, uint32_t, uint32_t left) {
+    if (tier != -2) return;
+    if (count0 >= 1024 && (uint64_t)left * 3 > (uint64_t)count0)
+      rhs.tiny_eager_256.store(1, std::memory_order_relaxed);
+    // the 128-tuple tier handed on nearly every string: skip the tiny tiers on this rhs
+    if (count0 >= 64 && (uint64_t)left * 10 > (uint64_t)count0 * 9 && !small)
+      rhs.skip_tiny_eager.store(1, std::memory_order_relaxed);
+  };
+  return run_bfs_ladder(count, list, list2, cnt, out.status, L, stream, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------
+// run_chain: one route per call
+// ---------------------------------------------------------------------------------
+
+namespace {
+enum class ChainRoute {
+  kEagerNan,      // a NaN weight in the rhs: every string UNSUPPORTED
+  kEagerReplay,   // negative weights: the general engine replaying the heap order
+  kEagerGeneral,  // rhs input epsilons: the general engine takes every string
+  kEagerTiers,    // layered lattices: tiers P, A0, A, B, C, then the general engine
+  kLazyDense,     // the LDS replays, then the band / dense replays
+  kLazyRounds,    // the lazy pull, the layered and the general rounds engines
+  kLazyHashed     // the hashed exact replay and its retries
+};
+
+// The route of a chain batch, from the rhs's flags, the semantics and FSTAMD_LAZY_ENGINE.
+// Eager: the order of the tests is the reference's (NaN has no order in its compare; with
+// negative weights shortest-path.zig's Dijkstra is not the exact SSSP the parallel engines
+// compute, so the general engine builds each lattice and replays the heap order on it:
+// sp_replay, kernels/eager_bfs.hpp).
+// Lazy: finite weights >= 0 -> the parallel rounds engines or the dense replay; otherwise
+// (+inf arcs, negative weights) the hashed exact replay.
+//  * rhs without input epsilons: the rounds route (the lazy pull, kernels/lazy_layered.hpp,
+//    then the general rounds engine, eager_bfs.hpp bfs_lazy_path, for the leftovers);
+//  * rhs with input epsilons: the dense route (kernels/lazy_dense.hpp) -- on epsilon-dense
+//    lattices nearly every tuple sits at one distance and the rounds degenerate to one pop
+//    each -- with the general rounds engine for its leftovers.  Small lattices too (config
+//    4's tagger and verbalizer: 15.2 ms per two-stage call of 64K utterances vs 18.4 ms in
+//    the hashed replay, whose per-wave tables live in HBM).
+// FSTAMD_LAZY_ENGINE=rounds | replay | dense forces one engine (A/B runs, tests); "lds": the
+// dense route with the LDS replay first whatever the rhs (tests: rhs without input epsilons).
+ChainRoute chain_route(const DeviceFst& rhs, int semantics) {
+  if (semantics == 1) {
+    if (rhs.nan) return ChainRoute::kEagerNan;
+    if (!rhs.nonneg) return ChainRoute::kEagerReplay;
+    return rhs.has_eps ? ChainRoute::kEagerGeneral : ChainRoute::kEagerTiers;
+  }
+  const char* le = std::getenv("FSTAMD_LAZY_ENGINE");
+  auto is = [le](const char* v) { return le && std::strcmp(le, v) == 0; };
+  if (!rhs.nonneg || !rhs.finite || is("replay")) return ChainRoute::kLazyHashed;
+  if (is("rounds")) return ChainRoute::kLazyRounds;
+  return is("dense") || is("lds") || rhs.has_eps ? ChainRoute::kLazyDense
+                                                 : ChainRoute::kLazyRounds;
+}
+}  // namespace
+
+// Whether the route's first tier is a pull tier (tier P of kEagerTiers, the lazy pull of
+// kLazyRounds).  Deliberately stricter than the route in two places, since its callers
+// stream labels into that tier and nothing else can take them: any FSTAMD_EAGER_TIER1
+// disables it (the route would still run tier P for a value it does not know), and any
+// non-empty FSTAMD_LAZY_ENGINE disables it (a value other than rounds, replay, dense or lds
+// still reaches kLazyRounds with the lazy pull on; pull_first refuses it all the same).
+bool DeviceEngine::pull_first(const DeviceFst& rhs, int semantics) {
+  if (rhs.has_eps) return false;
+  if (semantics == 1) {  // route_eager_tiers: use_p
+    if (rhs.nan || !rhs.nonneg || !rhs.pull_ok) return false;
+    return std::getenv("FSTAMD_EAGER_TIER1") == nullptr;
+  }
+  const char* le = std::getenv("FSTAMD_LAZY_ENGINE");  // route_lazy_rounds: use_lp
+  if (le && *le) return false;
+  return rhs.nonneg && rhs.finite && rhs.lazy_pull_ok;
+}
+
+hipError_t DeviceEngine::run_chain(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
+                                   int semantics, const BatchOutDev& out, hipStream_t stream,
+                                   LaunchStats* stats) {
+  HIP_TRY(hipSetDevice(dev_));
+  // the pull tiers alone copy paths out to the host (they must come first)
+  if (out.host_ol && !pull_first(rhs, semantics)) return hipErrorInvalidValue;
+  // host_w goes with host_ol: alone it would be BatchOutDev::text, which is launch_pull_part's
+  // (the streamed text batch) -- the tiers here read 4-B labels and emit no text
+  if (out.host_w && !out.host_ol) return hipErrorInvalidValue;
+  unsigned int* counter = (unsigned int*)scratch(kCounter, kCounterBytes);
+  if (!counter) return hipErrorOutOfMemory;
+  HIP_TRY(hipMemsetAsync(counter, 0, kCtrPrologueWords * 4, stream));
+  HIP_TRY(hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), stream));
+  if (in.num_strings == 0) return hipSuccess;
+  // every string starts as INTERNAL: a string no kernel finished can never read as a result
+  // (after launch_pull_part the statuses are the pull tier's)
+  if (!after_pull_)
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out.status, kPathInternal, in.num_strings, stream));
+  switch (chain_route(rhs, semantics)) {
+    case ChainRoute::kEagerNan:
+      mark_status_kernel<<<(in.num_strings + 255) / 256, 256, 0, stream>>>(in.num_strings, n,
+                                                                           rhs.view.start, out);
+      return hipGetLastError();
+    case ChainRoute::kEagerReplay:
+      if (stats) stats->engine = 6;
+      return timed(stats, stream,
+                   [&] { return run_bfs_chain(rhs, in, n, out, stream, true, false, true); });
+    case ChainRoute::kEagerGeneral:
+      if (stats) stats->engine = 2;
+      return timed(stats, stream, [&] { return run_bfs_chain(rhs, in, n, out, stream, true); });
+    case ChainRoute::kEagerTiers:
+      return route_eager_tiers(rhs, in, n, out, stream, stats, counter);
+    case ChainRoute::kLazyDense:
+      return route_lazy_dense(rhs, in, n, out, stream, stats, counter);
+    case ChainRoute::kLazyRounds:
+      return route_lazy_rounds(rhs, in, n, out, stream, stats, counter);
+    case ChainRoute::kLazyHashed:
+      return route_lazy_hashed(rhs, in, n, out, stream, stats, counter);
+  }
+  return hipErrorInvalidValue;
+}
+
+// Tier chain for layered lattices (each tier takes the strings the previous one reports as
+// OVERFLOW, through a device-side list):
+//   P  one wavefront per string, pull over the reverse mirror, window of kPullW states
+//      (when the rhs has one: DeviceFst::pull_ok)
+//   A0 one wavefront per string, direct-mapped LDS window of kEwinW target states
+//   A  one wavefront per string, LDS hash, <= kEwFcap tuples/layer, spans <= kEwKmax
+//   B  256 threads per string, LDS tables, <= kElFcap tuples/layer, spans <= kElKmax
+//   C  256 threads per string, HBM tables sized by the rhs (any layer)
+// FSTAMD_EAGER_TIER1=window starts at A0, =wave at A, =wg at B (A/B comparisons).  A
+// tier is skipped when the previous one provably cannot overflow on this rhs.
+hipError_t DeviceEngine::route_eager_tiers(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
+                                           const BatchOutDev& out, hipStream_t stream,
+                                           LaunchStats* stats, unsigned int* counter) {
+  const uint32_t num = in.num_strings;
+  const char* t1 = std::getenv("FSTAMD_EAGER_TIER1");
+  const bool start_b = t1 && std::strcmp(t1, "wg") == 0;
+  const bool use_w = !start_b && !(t1 && std::strcmp(t1, "wave") == 0);
+  const bool use_p = use_w && rhs.pull_ok && !(t1 && std::strcmp(t1, "window") == 0);
+  const uint32_t ns = rhs.view.num_states, ms = rhs.view.max_span;
+  auto back_cap_for = [&](uint32_t fcap, uint64_t limit, bool* capped) {
+    const uint64_t want = (uint64_t)(in.max_len + 1) * fcap;
+    *capped = want > limit;
+    return (uint32_t)std::min<uint64_t>(want, limit);
+  };
+  bool cap_w = false, cap_a = false, cap_b = false;
+  const uint32_t back_cap_w = back_cap_for(kEwinW, 1u << 22, &cap_w);
+  const uint32_t back_cap_a = back_cap_for(kEwFcap, 1u << 22, &cap_a);
+  const uint32_t back_cap_b = back_cap_for(kElFcap, 1u << 22, &cap_b);
+  // A0 overflows on a window wider than kEwinW or an expanded layer of more than
+  // 64 * kEwinEmax tuples (both impossible with <= 64 * kEwinEmax states), on a span
+  // longer than kEwinKmax and on its back slab; only the first two are A's business.
+  const bool use_a = !start_b && (!use_w || ns > (uint32_t)(64 * kEwinEmax));
+  const bool need_b = !(use_w || use_a) || ns > (uint32_t)kEwFcap || ms > (uint32_t)kEwKmax ||
+                      (use_a && cap_a) || (use_w && (ms > (uint32_t)kEwinKmax || cap_w));
+  const bool need_c = need_b && (ns > (uint32_t)kElFcap || ms > (uint32_t)kElKmax || cap_b);
+  auto k_win = eager_window_kernel<kEwinEmax, kEwinRows, kEwinKmax, kEwinWaves>;
+  if (const char* ww = std::getenv("FSTAMD_EWIN_WAVES")) {  // occupancy experiments
+    if (std::strcmp(ww, "2") == 0) k_win = eager_window_kernel<kEwinEmax, kEwinRows, kEwinKmax, 2>;
+    if (std::strcmp(ww, "4") == 0) k_win = eager_window_kernel<kEwinEmax, kEwinRows, kEwinKmax, 4>;
+  }
+  auto k_wave = eager_wave_kernel<kEwFcap, kEwHcap, kEwEmax, kEwKmax>;
+  auto k_wg = eager_layered_lds_kernel<kElWG, kElFcap, kElHcap, kElKmax>;
+  auto grid_for = [&](const void* k, int block, uint32_t back_cap) -> uint32_t {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, block, 0) != hipSuccess) occ = 1;
+    uint32_t g = (uint32_t)std::min<uint64_t>((uint64_t)std::max(occ, 1) * num_cus_, num);
+    while (g > 1 && (uint64_t)g * back_cap * sizeof(uint2) > (4ull << 30)) g /= 2;
+    return std::max<uint32_t>(g, 1);
+  };
+  // A0 keeps kChaseBatch back slabs per wave (backtraces are walked in batches)
+  uint32_t grid_w = 0;
+  if (use_w) {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_win, 64, 0) !=
+        hipSuccess)
+      occ = 1;
+    grid_w = (uint32_t)std::min<uint64_t>((uint64_t)std::max(occ, 1) * num_cus_, num);
+    // behind tier P, A0 only takes P's overflows: 2 waves per CU keep its slabs small
+    if (use_p) grid_w = std::min<uint32_t>(grid_w, 2u * (uint32_t)num_cus_);
+    while (grid_w > 1 && (uint64_t)grid_w * kChaseBatch * back_cap_w * 8 > (24ull << 30))
+      grid_w /= 2;
+    grid_w = std::max<uint32_t>(grid_w, 1);
+  }
+  // P: kChaseBatch back slabs per wave too, kPullW slots per layer
+  uint32_t grid_p = 0;
+  uint2* back_p = nullptr;
+  uint32_t* list_pw = nullptr;
+  if (use_p) {
+    grid_p = (uint32_t)std::min<uint64_t>((uint64_t)pull_waves_per_cu(rhs, in.max_len) * num_cus_,
+                                          num);
+    grid_p = std::min<uint32_t>(grid_p, grid_cap("FSTAMD_P_GRID"));
+    while (grid_p > 1 && (uint64_t)grid_p * kChaseBatch * back_cap_w * 8 > (24ull << 30))
+      grid_p /= 2;
+    grid_p = std::max<uint32_t>(grid_p, 1);
+    back_p = (uint2*)scratch(kPullBack, (size_t)grid_p * kChaseBatch * back_cap_w * 8);
+    list_pw = (uint32_t*)scratch(kItems4, (size_t)num * 4);
+    if (!back_p || !list_pw) return hipErrorOutOfMemory;
+  }
+  const uint32_t grid_a = use_a ? grid_for((const void*)k_wave, 64, back_cap_a) : 0;
+  const uint32_t grid_b = need_b ? grid_for((const void*)k_wg, kElWG, back_cap_b) : 0;
+  uint2* back_w =
+      use_w ? (uint2*)scratch(kElBackW, (size_t)grid_w * kChaseBatch * back_cap_w * 8) : nullptr;
+  uint2* back_a = use_a ? (uint2*)scratch(kElBack, (size_t)grid_a * back_cap_a * 8) : nullptr;
+  uint2* back_b = need_b ? (uint2*)scratch(kElBackB, (size_t)grid_b * back_cap_b * 8) : nullptr;
+  if ((use_w && !back_w) || (use_a && !back_a) || (need_b && !back_b))
+    return hipErrorOutOfMemory;
+  uint32_t* list_wa = (use_w && use_a) ? (uint32_t*)scratch(kItems3, (size_t)num * 4) : nullptr;
+  uint32_t* list_ab =
+      ((use_w || use_a) && need_b) ? (uint32_t*)scratch(kItems, (size_t)num * 4) : nullptr;
+  uint32_t* list_bc = need_c ? (uint32_t*)scratch(kItems2, (size_t)num * 4) : nullptr;
+  if ((use_w && use_a && !list_wa) || ((use_w || use_a) && need_b && !list_ab) ||
+      (need_c && !list_bc))
+    return hipErrorOutOfMemory;
+  uint32_t grid_c = 0, fcap_c = 0, hcap_c = 0, back_cap_c = 0;
+  uint8_t* slab_c = nullptr;
+  uint2* back_c = nullptr;
+  if (need_c) {
+    fcap_c = std::max<uint32_t>(ns, 1);
+    hcap_c = next_pow2(2ull * fcap_c);
+    back_cap_c = (uint32_t)std::min<uint64_t>((uint64_t)(in.max_len + 1) * fcap_c, 1u << 28);
+    const uint64_t per_wg = layer_slab_bytes(fcap_c, hcap_c) + (uint64_t)back_cap_c * 8;
+    grid_c = (uint32_t)std::min<uint64_t>(num_cus_, std::max<uint64_t>(1, (8ull << 30) / per_wg));
+    slab_c = (uint8_t*)scratch(kElSlab, (size_t)grid_c * layer_slab_bytes(fcap_c, hcap_c));
+    back_c = (uint2*)scratch(kElBack2, (size_t)grid_c * back_cap_c * sizeof(uint2));
+    if (!slab_c || !back_c) return hipErrorOutOfMemory;
+  }
+  if (stats) {
+    stats->engine = 0;
+    stats->grid = use_p ? grid_p : use_w ? grid_w : use_a ? grid_a : grid_b;
+    stats->launches = (use_p ? 2 : 0) + (use_w ? 1 : 0) + (use_a ? (use_w ? 2 : 1) : 0) +
+                      (need_b ? ((use_w || use_a) ? 2 : 1) : 0) + (need_c ? 2 : 0);
+  }
+  const unsigned long long wd = watchdog_ticks();
+  const HandSrc overflowed = with_status(num);
+  // (the bracket opens here: after the scratch allocations, before the first launch.  The
+  // hand-overs are the collect half only: each tier reads its list and count on the device)
+  return timed(stats, stream, [&]() -> hipError_t {
+    if (use_p) {
+      EagerLaunch lp{nullptr, nullptr, num, nullptr, 0, 0, back_p, back_cap_w, wd};
+      if (!after_pull_)
+        HIP_TRY(launch_eager_pull(rhs, in, n, counter + kCtrItemP, lp, out, grid_p, stream));
+      // test hook: FSTAMD_EAGER_ONLY_FIRST leaves tier P's OVERFLOW / UNSUPPORTED strings
+      // as they are, so a test can tell what the tier itself took
+      if (std::getenv("FSTAMD_EAGER_ONLY_FIRST")) return hipSuccess;
+    }
+    if (use_w) {
+      EagerLaunch lw{nullptr, nullptr, num, nullptr, 0, 0, back_w, back_cap_w, wd};
+      if (use_p) {
+        HIP_TRY(collect(overflowed, out.status, list_pw, counter + kCtrListPW, stream));
+        lw.items = list_pw;
+        lw.num_items_dev = counter + kCtrListPW;
+      }
+#ifdef FSTAMD_DEBUG_WAIT
+      HIP_TRY(debug_trace_arm());
+#endif
+      k_win<<<grid_w, 64, 0, stream>>>(rhs.view, in, n, counter + kCtrItemA0, lw, out);
+      HIP_TRY(hipGetLastError());
+#ifdef FSTAMD_DEBUG_WAIT
+      HIP_TRY(debug_wait(stream, grid_w, "tierA0"));
+#endif
+    }
+    if (use_a) {
+      EagerLaunch la{nullptr, nullptr, num, nullptr, 0, 0, back_a, back_cap_a, wd};
+      if (use_w) {
+        HIP_TRY(collect(overflowed, out.status, list_wa, counter + kCtrListWA, stream));
+        la.items = list_wa;
+        la.num_items_dev = counter + kCtrListWA;
+      }
+#ifdef FSTAMD_DEBUG_WAIT
+      HIP_TRY(debug_trace_arm());
+#endif
+      k_wave<<<grid_a, 64, 0, stream>>>(rhs.view, in, n, counter + kCtrItemA, la, out);
+      HIP_TRY(hipGetLastError());
+#ifdef FSTAMD_DEBUG_WAIT
+      HIP_TRY(debug_wait(stream, grid_a, "tierA"));
+#endif
+    }
+    if (need_b) {
+      EagerLaunch lb{nullptr, nullptr, num, nullptr, 0, 0, back_b, back_cap_b, wd};
+      if (use_w || use_a) {
+        HIP_TRY(collect(overflowed, out.status, list_ab, counter + kCtrListAB, stream));
+        lb.items = list_ab;
+        lb.num_items_dev = counter + kCtrListAB;
+      }
+      k_wg<<<grid_b, kElWG, 0, stream>>>(rhs.view, in, n, counter + kCtrItemB, lb, out);
+      HIP_TRY(hipGetLastError());
+#ifdef FSTAMD_DEBUG_WAIT
+      HIP_TRY(debug_wait(stream, grid_b, "tierB"));
+#endif
+    }
+    if (need_c) {
+      HIP_TRY(collect(overflowed, out.status, list_bc, counter + kCtrListBC, stream));
+      EagerLaunch lc{list_bc, counter + kCtrListBC, 0, slab_c, fcap_c, hcap_c, back_c, back_cap_c,
+                     wd};
+      eager_layered_kernel<kElWG, kElFcap, kElHcap, false>
+          <<<grid_c, kElWG, 0, stream>>>(rhs.view, in, n, counter + kCtrItemC, lc, out);
+      HIP_TRY(hipGetLastError());
+#ifdef FSTAMD_DEBUG_WAIT
+      HIP_TRY(debug_wait(stream, grid_c, "tierC"));
+#endif
+    }
+    if (std::getenv("FSTAMD_ROUTE_LOG")) {  // how many strings each fallback tier took
+      unsigned int h[kCtrPrologueWords] = {};
+      HIP_TRY(hipMemcpyAsync(h, counter, sizeof(h), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      std::fprintf(stderr,
+                   "[libfst_amd route] eager: %u strings, tiers P %d A0 %d A %d B %d C %d | "
+                   "handed on: P->A0 %u, A0->A %u, ->B %u, ->C %u\n",
+                   num, (int)use_p, (int)use_w, (int)use_a, (int)need_b, (int)need_c,
+                   use_p && use_w ? h[kCtrListPW] : 0u, use_w && use_a ? h[kCtrListWA] : 0u,
+                   need_b && (use_w || use_a) ? h[kCtrListAB] : 0u, need_c ? h[kCtrListBC] : 0u);
+    }
+    // Strings the layered tiers cannot take (label-0 inputs -> UNSUPPORTED, tier-2
+    // OVERFLOW) go to the general BFS engine.
+    return run_bfs_chain(rhs, in, n, out, stream, false);
+  });
+}
+
+// The dense route's LDS replays: the replay with the wave's tables in LDS (run_lazy_tiny) at
+// growing sizes -- every string at 1024 tuples when the batch is small enough (direct), else
+// 128 and / or 256 -- then 512 and 1024 for what is left, then the hashed replay (HBM tables,
+// x8 per retry) when the LDS sizes took most of the batch.  Returns (*todo, *todo_n): the
+// device list of the strings still OVERFLOW, for the band and dense replays, and its length
+// as the host knows it; the strings it finished have their results.
+hipError_t DeviceEngine::lazy_lds_sizes(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
+                                        const BatchOutDev& out, hipStream_t stream,
+                                        LaunchStats* stats, unsigned int* ctr,
+                                        const uint32_t** todo, uint32_t* todo_n) {
+  const uint32_t num = in.num_strings;
+  uint32_t* la = (uint32_t*)scratch(kItems, (size_t)num * 4);
+  uint32_t* lb = (uint32_t*)scratch(kItems2, (size_t)num * 4);
+  if (!la || !lb) return hipErrorOutOfMemory;
+  HIP_TRY(hipMemsetAsync(ctr + kCtrLds128Item, 0, 16, stream));
+  uint32_t g = 0;
+  // the 128-tuple size first, unless it handed on over a third of an earlier batch on
+  // this rhs (DeviceFst::tiny_lazy_256: the WeText-scale tagger's lattices, 54 % over
+  // 128 tuples: tagger stage 46.7 -> 40.0 ms per 64 K utterances starting at 256);
+  // FSTAMD_LAZY_TINY_START=1|2 forces the first size
+  const char* ts = std::getenv("FSTAMD_LAZY_TINY_START");
+  const bool first128 = ts && *ts ? std::strcmp(ts, "2") != 0
+                                  : rhs.tiny_lazy_256.load(std::memory_order_relaxed) == 0;
+  uint32_t cnt[2] = {0, 0};
+  // A batch that the largest LDS size holds at once (coalesced single calls, small host
+  // batches) starts every string there: one wave per string whichever the size, so a
+  // long utterance no longer pays a replay at 256 tuples before its rerun at 512 or 1024
+  // (36 B per tuple: 1024 tuples are 38 KB, 4 waves per CU)
+  const bool direct = !(ts && *ts) && (uint64_t)num <= (uint64_t)num_cus_ *
+                                                           waves_per_cu<lazy_tiny_kernel<4>>();
+  const HandSrc every = with_status(num);
+  if (direct) {
+    HIP_TRY(run_lazy_tiny(rhs, in, n, out, stream, 4, nullptr, num, ctr + kCtrLds256Item, &g));
+    if (stats) stats->grid = g;
+    HIP_TRY(hand_on(every, out.status, lb, ctr + kCtrLds256List, &cnt[1], stream));
+    if (num >= 64 && (uint64_t)cnt[1] * 10 > (uint64_t)num * 9)
+      rhs.skip_tiny_lazy.store(1, std::memory_order_relaxed);
+  } else if (first128) {
+    HIP_TRY(run_lazy_tiny(rhs, in, n, out, stream, 1, nullptr, num, ctr + kCtrLds128Item, &g));
+    if (stats) stats->grid = g;
+    HIP_TRY(hand_on(every, out.status, la, ctr + kCtrLds128List, &cnt[0], stream));
+  } else {
+    cnt[0] = num;
+  }
+  if (!direct && cnt[0] > 0) {
+    HIP_TRY(run_lazy_tiny(rhs, in, n, out, stream, 2, first128 ? la : nullptr, cnt[0],
+                          ctr + kCtrLds256Item, &g));
+    HIP_TRY(hand_on(first128 ? from_list(la, ctr + kCtrLds128List, cnt[0]) : every, out.status,
+                    lb, ctr + kCtrLds256List, &cnt[1], stream));
+    if (stats) stats->launches += 1;
+  }
+  if (!direct && first128 && num >= 1024 && (uint64_t)cnt[0] * 3 > (uint64_t)num)
+    rhs.tiny_lazy_256.store(1, std::memory_order_relaxed);
+  if (!direct && first128 && num < 1024) {  // small batches: the same rule over their sum
+    const uint64_t seen = rhs.tiny_lazy_seen.fetch_add(num) + num;
+    const uint64_t over = rhs.tiny_lazy_over.fetch_add(cnt[0]) + cnt[0];
+    if (seen >= 1024 && over * 3 > seen) rhs.tiny_lazy_256.store(1, std::memory_order_relaxed);
+  }
+  if (!direct && first128 && num >= 64 && (uint64_t)cnt[0] * 10 > (uint64_t)num * 9)
+    rhs.skip_tiny_lazy.store(1, std::memory_order_relaxed);
+  *todo_n = cnt[1];
+  uint32_t* rest = lb;  // the strings still OVERFLOW, and their count (device)
+  unsigned int* rest_cnt = ctr + kCtrLds256List;
+  uint32_t* spare = la;
+  unsigned int* spare_cnt = ctr + kCtrLds128List;
+  // Larger LDS sizes for the outliers of the LDS replays, or for every string of a small
+  // batch (a coalesced single call: a long utterance, ~400-900 tuples, went to the dense
+  // replay's HBM index -- 2.7 ms for 63 labels of the WeText-scale tagger): 512 tuples
+  // (~55 KB, 2 waves per CU), then 1024 (~110 KB, 1 per CU), one string per wave.
+  uint32_t cnt_big[2] = {0, 0};
+  for (int t = 3;
+       !direct && t <= 4 && *todo_n > 0 && ((uint64_t)*todo_n * 4 <= num || num <= 64); ++t) {
+    unsigned int* item = ctr + (t == 3 ? kCtrLds512Item : kCtrLds1024Item);
+    unsigned int* left = ctr + (t == 3 ? kCtrLds512List : kCtrLds1024List);  // the next word
+    HIP_TRY(hipMemsetAsync(item, 0, 8, stream));
+    HIP_TRY(run_lazy_tiny(rhs, in, n, out, stream, t, rest, *todo_n, item, &g));
+    HIP_TRY(hand_on(from_list(rest, rest_cnt, *todo_n), out.status, spare, left, todo_n, stream));
+    cnt_big[t - 3] = *todo_n;
+    std::swap(rest, spare);
+    spare_cnt = rest_cnt;
+    rest_cnt = left;
+    if (stats) stats->launches += 1;
+  }
+  // The LDS replays took most strings (>= 3/4): the rest are small-lattice outliers,
+  // served by the hashed replay (HBM tables sized by the lattice, x8 per retry) rather
+  // than by the dense index sized by (L + 1) * NS (a WeText-scale tagger: 1.6 GB per
+  // wave).  When they took few (large lattices), the dense replay takes the rest.
+  if (*todo_n > 0 && (uint64_t)*todo_n * 4 <= num) {
+    uint64_t want = 4096;
+    for (int t = 0; t < 4 && *todo_n > 0; ++t, want *= 8) {
+      HIP_TRY(hipMemsetAsync(ctr + kCtrLdsHashedItem, 0, 4, stream));
+      if (launch_lazy_hashed(rhs, in, n, out, stream, want, rest, *todo_n,
+                             ctr + kCtrLdsHashedItem, &g) != hipSuccess)
+        break;  // beyond its budget: the strings stay OVERFLOW for the dense replay
+      HIP_TRY(hipMemsetAsync(spare_cnt, 0, 4, stream));
+      HIP_TRY(hand_on(from_list(rest, rest_cnt, *todo_n), out.status, spare, spare_cnt, todo_n,
+                      stream));
+      std::swap(rest, spare);
+      std::swap(rest_cnt, spare_cnt);
+      if (stats) stats->launches += 1;
+    }
+  }
+  *todo = rest;
+  if (std::getenv("FSTAMD_ROUTE_LOG"))
+    std::fprintf(stderr,
+                 "[libfst_amd route] lazy: %u strings, LDS-128 handed on %u, LDS-256 %u, "
+                 "LDS-512 %u, LDS-1024 %u, to the dense replay %u\n",
+                 num, cnt[0], cnt[1], cnt_big[0], cnt_big[1], *todo_n);
+  return hipSuccess;
+}
+
+hipError_t DeviceEngine::route_lazy_dense(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
+                                          const BatchOutDev& out, hipStream_t stream,
+                                          LaunchStats* stats, unsigned int* counter) {
+  const char* le = std::getenv("FSTAMD_LAZY_ENGINE");
+  const bool force_dense = le && std::strcmp(le, "dense") == 0;
+  const char* lte = std::getenv("FSTAMD_LAZY_TINY");
+  if (stats) {
+    stats->engine = 5;
+    stats->launches = 1;
+  }
+  return timed(stats, stream, [&]() -> hipError_t {
+    // Small lattices first, whatever the rhs size: the replay with the wave's tables in
+    // LDS at 128, then 256 tuples.  A WeText-scale tagger has 0.4 M states but ~140 tuples
+    // per utterance, while the dense replay's per-wave index is (L + 1) * NS * 2 tuples (1.6
+    // GB per wave there): it takes only what outgrows the LDS.  An rhs whose strings nearly
+    // all outgrow it (config 3's lattices of millions of tuples) skips the LDS pass from
+    // then on (DeviceFst::skip_tiny_lazy); FSTAMD_LAZY_TINY=0 skips it always.
+    const bool small = !force_dense && !(lte && std::strcmp(lte, "0") == 0) &&
+                       rhs.skip_tiny_lazy.load(std::memory_order_relaxed) == 0 &&
+                       in.num_strings > 0;
+    const uint32_t* todo = nullptr;  // the dense replay's strings (nullptr: all)
+    uint32_t todo_n = in.num_strings;
+    if (small) HIP_TRY(lazy_lds_sizes(rhs, in, n, out, stream, stats, counter, &todo, &todo_n));
+    // the LDS (and hashed) replays took every string: they leave none UNSUPPORTED, so there
+    // is nothing for the band, dense or general engines -- and the general engine's count
+    // readback would cost the call a synchronisation (the band and dense replays do mark
+    // strings UNSUPPORTED, so this holds only when neither runs)
+    const bool all_done = small && todo_n == 0;
+    bool ran = true;
+    if (todo_n > 0) {
+      // the band replay first (rhs whose arcs all go forward: config 3), the dense replay
+      // for what it hands on
+      // With the exact early exit a string only reaches ~2 L states past the start
+      // (config 3: DESIGN.md §4.2c), so the first launch keeps back pointers for a few
+      // windows of states; what reaches further runs again over the whole rhs.
+      const bool early_ok = rhs.nonneg && rhs.finite && !std::getenv("FSTAMD_NO_EARLY");
+      for (int pass = early_ok ? 0 : 1; pass < 2 && todo_n > 0; ++pass) {
+        bool band = false;
+        HIP_TRY(run_lazy_band(rhs, in, n, out, stream, &band, todo, todo ? todo_n : 0,
+                              pass == 0));
+        if (!band) break;
+        if (stats) stats->launches += 1;
+        // (the list `todo` may be kItems or kItems2: the next one goes elsewhere)
+        uint32_t* la = (uint32_t*)scratch(pass == 0 ? kItems3 : kItems4,
+                                          (size_t)in.num_strings * 4);
+        if (!la) return hipErrorOutOfMemory;
+        HIP_TRY(hipMemsetAsync(counter + kCtrBandList, 0, 4, stream));
+        HIP_TRY(hand_on(with_status(in.num_strings), out.status, la, counter + kCtrBandList,
+                        &todo_n, stream));
+        todo = la;
+        if (std::getenv("FSTAMD_ROUTE_LOG"))
+          std::fprintf(stderr, "[libfst_amd route] lazy: band replay (%s) handed on %u\n",
+                       pass == 0 ? "capped, early exit" : "whole rhs", todo_n);
+      }
+    }
+    if (todo_n > 0) {
+      HIP_TRY(run_lazy_dense(rhs, in, n, out, stream, &ran, todo, todo ? todo_n : 0));
+      if (stats) stats->launches += 1;
+    }
+    if (stats && !ran) stats->engine = 3;  // too large for the dense engine: rounds only
+    if (!std::getenv("FSTAMD_DENSE_NOFALLBACK") && !all_done)  // debug: leave UNSUPPORTED
+      HIP_TRY(run_bfs_chain(rhs, in, n, out, stream, !ran && !small, true));
+    return hipSuccess;
+  });
+}
+
+hipError_t DeviceEngine::route_lazy_rounds(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
+                                           const BatchOutDev& out, hipStream_t stream,
+                                           LaunchStats* stats, unsigned int*) {
+  if (stats) stats->engine = 3;
+  return timed(stats, stream, [&]() -> hipError_t {
+    // Layered lattices (no rhs input epsilon; label-0 inputs are sent on as UNSUPPORTED):
+    // the one-wave dense engine (kernels/lazy_layered.hpp), FSTAMD_LAZY_LAYERED=0 skips
+    // it; the general rounds engine takes everything else and its leftovers.
+    const char* ll = std::getenv("FSTAMD_LAZY_LAYERED");
+    const bool layered = !rhs.has_eps && rhs.view.max_span <= kLlSpanMax &&
+                         (uint64_t)(in.max_len + 1) * rhs.view.num_states <= kLlDenseMax &&
+                         !(ll && std::strcmp(ll, "0") == 0);
+    // Layer-local pull first (kernels/lazy_pull.hpp) when the rhs has a reverse mirror
+    // that suits it; the strings it hands on go to the rounds engines.
+    const char* le = std::getenv("FSTAMD_LAZY_ENGINE");
+    const bool force_rounds = le && std::strcmp(le, "rounds") == 0;
+    const bool use_lp = !rhs.has_eps && rhs.lazy_pull_ok && !force_rounds;
+    uint32_t* lp_list = nullptr;
+    uint32_t* lp_count = nullptr;
+    if (use_lp) {
+      if (stats) stats->engine = 7;
+      HIP_TRY(run_lazy_pull(rhs, in, n, out, stream, &lp_list, &lp_count, !after_pull_));
+      // test hook: what the pull took alone
+      if (std::getenv("FSTAMD_LAZY_ONLY_FIRST")) return hipSuccess;
+    }
+    if (layered) {
+      if (stats && !use_lp) stats->engine = 4;
+      HIP_TRY(run_lazy_layered(rhs, in, n, out, stream, lp_list, lp_count));
+    }
+    return run_bfs_chain(rhs, in, n, out, stream, !layered && !use_lp, true);
+  });
+}
+
+// The hashed exact replay: the per-wave workspace is sized from max_len; strings that
+// outgrow it (OVERFLOW) are re-run from a list with 8x the capacity and fewer waves, until
+// they fit or the budget is exhausted.  It starts small lattices with its tables in LDS, then
+// HBM for what outgrows them; FSTAMD_LAZY_TINY=0 skips that.  (As the engine for config 4's
+// small epsilon lattices it measured level with the dense replay, 15.8 vs 15.0 ms per
+// two-stage call: the pop's rhs reads and shuffles bind, not the tables.)
+hipError_t DeviceEngine::route_lazy_hashed(const DeviceFst& rhs, const ChainInput& in, uint32_t n,
+                                           const BatchOutDev& out, hipStream_t stream,
+                                           LaunchStats* stats, unsigned int* counter) {
+  const uint32_t num = in.num_strings;
+  const char* lte = std::getenv("FSTAMD_LAZY_TINY");
+  const bool tiny_first = !(lte && std::strcmp(lte, "0") == 0) &&
+                          (uint64_t)(in.max_len + 1) * rhs.view.num_states <= 16384;
+  uint64_t want = std::max<uint64_t>(4096, (uint64_t)256 * (in.max_len + 1));
+  if (stats) {
+    stats->engine = 1;
+    stats->launches = 1;
+  }
+  return timed(stats, stream, [&]() -> hipError_t {
+    uint32_t grid0 = 0;
+    if (tiny_first) {  // LDS tables (kernels/lazy_wave.hpp, 128 tuples)
+      HIP_TRY(run_lazy_tiny(rhs, in, n, out, stream, 1, nullptr, num, counter + kCtrItemFirst,
+                            &grid0));
+    } else {
+      HIP_TRY(launch_lazy_hashed(rhs, in, n, out, stream, want, nullptr, num,
+                                 counter + kCtrItemFirst, &grid0));
+    }
+    if (stats) stats->grid = grid0;
+    // retry tiers for OVERFLOW strings (host reads the count: this path is for outliers)
+    uint32_t* list = (uint32_t*)scratch(kItems, (size_t)num * 4);
+    if (!list) return hipErrorOutOfMemory;
+    for (int tier = 1; tier <= 4; ++tier) {
+      unsigned int* item = counter + ctr_retry(tier);
+      unsigned int* left = counter + ctr_retry_list(tier);
+      HIP_TRY(hipMemsetAsync(item, 0, 8, stream));  // both: the list count is the next word
+      uint32_t cnt = 0;
+      HIP_TRY(hand_on(with_status(num), out.status, list, left, &cnt, stream));
+      if (cnt == 0) break;
+      if (!(tiny_first && tier == 1)) want *= 8;  // after the tiny launch: HBM at `want` first
+      uint32_t g = 0;
+      if (launch_lazy_hashed(rhs, in, n, out, stream, want, list, cnt, item, &g) != hipSuccess)
+        break;  // stays OVERFLOW
+      if (stats) stats->launches += 2;
+    }
+    return hipSuccess;
+  });
 }
 
 hipError_t DeviceEngine::compose_lattice(const DeviceFst& rhs, const GraphInput& lhs,
@@ -2290,19 +2368,19 @@ hipError_t DeviceEngine::compose_lattice(const DeviceFst& rhs, const GraphInput&
     ws.lcap = c.lcap;
     ws.wd_ticks = watchdog_ticks();
     ws.lattice_only = 1;
-    HIP_TRY(hipMemsetAsync(ctr, 0, 64, stream));
-    if (stats) HIP_TRY(hipEventRecord(ev0_, stream));
-    ChainInput none{};
-    if (wg1k)
-      eager_bfs_kernel<1024, true><<<1, 1024, 0, stream>>>(rhs.view, none, lhs, 1, ctr, nullptr,
-                                                            nullptr, 1, ws, none_out);
-    else
-      eager_bfs_kernel<kBfsWG, true><<<1, kBfsWG, 0, stream>>>(rhs.view, none, lhs, 1, ctr,
-                                                                nullptr, nullptr, 1, ws, none_out);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(ctr, 0, kCtrPrologueWords * 4, stream));
+    HIP_TRY(timed(stats, stream, [&] {
+      ChainInput none{};
+      unsigned int* item = ctr + kCtrItemFirst;
+      if (wg1k)
+        eager_bfs_kernel<1024, true><<<1, 1024, 0, stream>>>(rhs.view, none, lhs, 1, item, nullptr,
+                                                              nullptr, 1, ws, none_out);
+      else
+        eager_bfs_kernel<kBfsWG, true><<<1, kBfsWG, 0, stream>>>(rhs.view, none, lhs, 1, item,
+                                                                  nullptr, nullptr, 1, ws, none_out);
+      return hipGetLastError();
+    }));
     if (stats) {
-      HIP_TRY(hipEventRecord(ev1_, stream));
-      HIP_TRY(finish_stats(ev0_, ev1_, stats));
       stats->engine = 2;
       stats->grid = 1;
       stats->launches = tier - tier0 + 1;
@@ -2374,13 +2452,12 @@ hipError_t DeviceEngine::shortest_path_graph(const GraphInput& g, uint32_t n,
     T.nfin = const_cast<double*>(g.final_w);
     T.nd = (unsigned long long*)w;
     T.nback = (unsigned long long*)(w + (size_t)N * 8);
-    if (stats) HIP_TRY(hipEventRecord(ev0_, stream));
-    sp_replay_kernel<<<1, 64, 0, stream>>>(T, N, g.start, n, (SpHeapEnt*)(w + nd_b + st_b),
-                                            hcap, w + nd_b, out, watchdog_ticks());
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(timed(stats, stream, [&] {
+      sp_replay_kernel<<<1, 64, 0, stream>>>(T, N, g.start, n, (SpHeapEnt*)(w + nd_b + st_b),
+                                              hcap, w + nd_b, out, watchdog_ticks());
+      return hipGetLastError();
+    }));
     if (stats) {
-      HIP_TRY(hipEventRecord(ev1_, stream));
-      HIP_TRY(finish_stats(ev0_, ev1_, stats));
       stats->engine = 6;
       stats->grid = 1;
       stats->launches = 1;
@@ -2414,51 +2491,51 @@ hipError_t DeviceEngine::shortest_path_graph(const GraphInput& g, uint32_t n,
   T.lvl = lv;
   T.nd = (unsigned long long*)w;
   T.nback = (unsigned long long*)(w + (size_t)N * 8);
-  if (stats) HIP_TRY(hipEventRecord(ev0_, stream));
-  // FSTAMD_SP_SWEEP=1: the Gauss-Seidel sweeps over every arc instead of the frontier
-  const bool sweep = std::getenv("FSTAMD_SP_SWEEP") != nullptr;
-  const bool hprof = std::getenv("FSTAMD_HOST_PROF") != nullptr;
-  hipEvent_t em = nullptr;
-  if (hprof) {
-    HIP_TRY(hipEventCreate(&em));
-    HIP_TRY(hipEventRecord(ev0_, stream));
-  }
-  // distances: settled in distance order (sp_settle_kernel); after more than
-  // FSTAMD_SP_MAX_ADV (256) distinct distances, label correcting (sp_frontier_kernel)
-  uint32_t sf[4] = {0, 0, 0, 0};  // fallback, expired, rounds, advances
-  if (!sweep && g.start < N && n == 1) {
-    const char* ma = std::getenv("FSTAMD_SP_MAX_ADV");
-    const uint32_t max_adv = ma ? (uint32_t)std::strtoul(ma, nullptr, 10) : 256u;
-    sp_settle_kernel<1024><<<1, 1024, 0, stream>>>(T, N, g.start, mark, stl, fa, fb, pend,
-                                                    lv + 4, max_adv, watchdog_ticks());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(copy_sync(sf, lv + 4, 16, hipMemcpyDeviceToHost, stream));
-    if (sf[1]) {  // its watchdog fired: the path reports INTERNAL
-      const uint32_t one = 1;
-      HIP_TRY(copy_sync(lv + 3, &one, 4, hipMemcpyHostToDevice, stream));
-    } else if (sf[0]) {
-      sp_frontier_kernel<1024><<<1, 1024, 0, stream>>>(T, N, g.start, mark, fa, fb, lv + 3,
-                                                        watchdog_ticks());
+  HIP_TRY(timed(stats, stream, [&]() -> hipError_t {
+    // FSTAMD_SP_SWEEP=1: the Gauss-Seidel sweeps over every arc instead of the frontier
+    const bool sweep = std::getenv("FSTAMD_SP_SWEEP") != nullptr;
+    const bool hprof = std::getenv("FSTAMD_HOST_PROF") != nullptr;
+    hipEvent_t em = nullptr;
+    if (hprof) {
+      HIP_TRY(hipEventCreate(&em));
+      HIP_TRY(hipEventRecord(ev0_, stream));
     }
-  }
-  if (hprof) HIP_TRY(hipEventRecord(em, stream));
-  sp_graph_kernel<1024><<<1, 1024, 0, stream>>>(
-      T, N, g.start, n, out, watchdog_ticks(), sweep || g.start >= N || n != 1 ? nullptr : lv + 2);
-  if (hprof) {
-    HIP_TRY(hipEventRecord(ev1_, stream));
-    HIP_TRY(hipEventSynchronize(ev1_));
-    float a = 0.f, b = 0.f;
-    HIP_TRY(hipEventElapsedTime(&a, ev0_, em));
-    HIP_TRY(hipEventElapsedTime(&b, em, ev1_));
-    std::fprintf(stderr, "[libfst_amd host] fst_shortest_path: distances %.2f ms (settle: %u "
-                 "rounds, %u advances%s), back-pointers + best + path %.2f ms (%u states)\n",
-                 a, sf[2], sf[3], sf[0] ? ", then label correcting" : "", b, N);
-    HIP_TRY(hipEventDestroy(em));
-  }
-  HIP_TRY(hipGetLastError());
+    // distances: settled in distance order (sp_settle_kernel); after more than
+    // FSTAMD_SP_MAX_ADV (256) distinct distances, label correcting (sp_frontier_kernel)
+    uint32_t sf[4] = {0, 0, 0, 0};  // fallback, expired, rounds, advances
+    if (!sweep && g.start < N && n == 1) {
+      const char* ma = std::getenv("FSTAMD_SP_MAX_ADV");
+      const uint32_t max_adv = ma ? (uint32_t)std::strtoul(ma, nullptr, 10) : 256u;
+      sp_settle_kernel<1024><<<1, 1024, 0, stream>>>(T, N, g.start, mark, stl, fa, fb, pend,
+                                                      lv + 4, max_adv, watchdog_ticks());
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(copy_sync(sf, lv + 4, 16, hipMemcpyDeviceToHost, stream));
+      if (sf[1]) {  // its watchdog fired: the path reports INTERNAL
+        const uint32_t one = 1;
+        HIP_TRY(copy_sync(lv + 3, &one, 4, hipMemcpyHostToDevice, stream));
+      } else if (sf[0]) {
+        sp_frontier_kernel<1024><<<1, 1024, 0, stream>>>(T, N, g.start, mark, fa, fb, lv + 3,
+                                                          watchdog_ticks());
+      }
+    }
+    if (hprof) HIP_TRY(hipEventRecord(em, stream));
+    sp_graph_kernel<1024><<<1, 1024, 0, stream>>>(
+        T, N, g.start, n, out, watchdog_ticks(),
+        sweep || g.start >= N || n != 1 ? nullptr : lv + 2);
+    if (hprof) {
+      HIP_TRY(hipEventRecord(ev1_, stream));
+      HIP_TRY(hipEventSynchronize(ev1_));
+      float a = 0.f, b = 0.f;
+      HIP_TRY(hipEventElapsedTime(&a, ev0_, em));
+      HIP_TRY(hipEventElapsedTime(&b, em, ev1_));
+      std::fprintf(stderr, "[libfst_amd host] fst_shortest_path: distances %.2f ms (settle: %u "
+                   "rounds, %u advances%s), back-pointers + best + path %.2f ms (%u states)\n",
+                   a, sf[2], sf[3], sf[0] ? ", then label correcting" : "", b, N);
+      HIP_TRY(hipEventDestroy(em));
+    }
+    return hipGetLastError();
+  }));
   if (stats) {
-    HIP_TRY(hipEventRecord(ev1_, stream));
-    HIP_TRY(finish_stats(ev0_, ev1_, stats));
     stats->engine = 2;
     stats->grid = 1;
     stats->launches = 1;
@@ -2523,8 +2600,9 @@ hipError_t DeviceEngine::project_output(const BatchOutDev& stage, uint32_t num,
                                         hipStream_t stream) {
   HIP_TRY(hipSetDevice(dev_));
   uint64_t* counts = (uint64_t*)scratch(kProjCount, ((size_t)num + 1) * 8 + 16);
-  uint32_t* ml = (uint32_t*)scratch(kCounter, kCounterBytes) + 15;
-  if (!counts || !ml) return hipErrorOutOfMemory;
+  uint32_t* ctr = (uint32_t*)scratch(kCounter, kCounterBytes);
+  if (!counts || !ctr) return hipErrorOutOfMemory;
+  uint32_t* ml = ctr + kCtrProjMaxLen;
   HIP_TRY(hipMemsetAsync(ml, 0, 4, stream));
   project_count_kernel<<<(num + 256) / 256, 256, 0, stream>>>(stage, num, counts, proj_status,
                                                              ml);
@@ -2668,7 +2746,7 @@ hipError_t DeviceEngine::run_graph(const DeviceFst& rhs, const GraphInput& in, u
   if (semantics != 0) return hipErrorInvalidValue;
   unsigned int* counter = (unsigned int*)scratch(kCounter, kCounterBytes);
   if (!counter) return hipErrorOutOfMemory;
-  HIP_TRY(hipMemsetAsync(counter, 0, 64, stream));
+  HIP_TRY(hipMemsetAsync(counter, 0, kCtrPrologueWords * 4, stream));
   HIP_TRY(hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), stream));
   LazyWs ws{};
   ws.ncap = next_pow2(std::max<uint32_t>(in.ncap, 1024));
@@ -2697,42 +2775,37 @@ hipError_t DeviceEngine::run_graph(const DeviceFst& rhs, const GraphInput& in, u
     stats->engine = 1;
     stats->grid = grid;
     stats->launches = 1;
-    HIP_TRY(hipEventRecord(ev0_, stream));
   }
-  ChainInput none{};
-  none.num_strings = 1;
-  lazy_wave_kernel<true><<<grid, 64, 0, stream>>>(rhs.view, none, in, n, counter, nullptr, 1, ws,
-                                                  out);
-  HIP_TRY(hipGetLastError());
-  if (stats) {
-    HIP_TRY(hipEventRecord(ev1_, stream));
-    HIP_TRY(finish_stats(ev0_, ev1_, stats));
-  }
-  return hipSuccess;
+  return timed(stats, stream, [&] {
+    ChainInput none{};
+    none.num_strings = 1;
+    lazy_wave_kernel<true><<<grid, 64, 0, stream>>>(rhs.view, none, in, n,
+                                                    counter + kCtrItemFirst, nullptr, 1, ws, out);
+    return hipGetLastError();
+  });
 }
 
 // ---- batch of general lhs (lhs_batch.hip holds the kernel instances) -------------------
 
-// The eager ladder of run_bfs_chain over a device list of batch items: the LDS sizes, tier 0
-// with one wave per item, then the 256-thread tiers x8; what a tier reports OVERFLOW moves to
-// the next through collect_list_kernel.  The heap replay starts at tier 0 (its heap is in HBM).
+// The ladder (run_bfs_ladder) over a device list of batch items, one wave per item at tier 0.
+// The heap replay starts at tier 0 (its heap is in HBM).
 hipError_t DeviceEngine::run_lhs_eager(const DeviceFst& rhs, const ChainInput& in,
                                        const GraphInput& lhs, uint32_t n, const uint32_t* items,
                                        uint32_t count, bool replay, const BatchOutDev& out,
                                        hipStream_t stream, LhsRoute* route, uint32_t* grid_out) {
   if (count == 0) return hipSuccess;
-  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);  // [8..11], as run_bfs_chain
+  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);
   uint32_t* list = (uint32_t*)scratch(kBfsList, (size_t)in.num_strings * 4);
   uint32_t* list2 = (uint32_t*)scratch(kBfsList2, (size_t)in.num_strings * 4);
   if (!ctr || !list || !list2) return hipErrorOutOfMemory;
-  uint32_t* cnt = ctr + 8;
-  HIP_TRY(hipMemsetAsync(cnt, 0, 32, stream));
+  uint32_t* cnt = ctr + kCtrBfsCount;
+  HIP_TRY(hipMemsetAsync(cnt, 0, kCtrBfsWords * 4, stream));
   HIP_TRY(hipMemcpyAsync(cnt, &count, 4, hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(list, items, (size_t)count * 4, hipMemcpyDeviceToDevice, stream));
   BfsLadder L;
-  L.tiny = !replay;
+  L.first = replay ? 0 : -2;
   L.replay = replay;
-  L.lattice_only = 0;
+  L.grid_cap = grid_cap("FSTAMD_GRAPH_GRID");
   L.per_cu = [](int kind) { return lhs_eager_per_cu(kind); };
   L.launch = [&](int kind, const BfsWs& ws, unsigned int* next_item, const uint32_t* cur,
                  const uint32_t* cur_count, uint32_t grid) {
@@ -2740,66 +2813,6 @@ hipError_t DeviceEngine::run_lhs_eager(const DeviceFst& rhs, const ChainInput& i
                             stream);
   };
   return run_bfs_ladder(count, list, list2, cnt, out.status, L, stream, route, grid_out);
-}
-
-// The ladder itself, shared by run_lhs_eager and run_lattice_batch: `list` holds `count`
-// items and cnt[0] = count on the device; cnt[1] is the item counter, cnt[2] the next list's
-// count.  L.launch queues one tier's kernel; L.per_cu gives an LDS tier's resident workgroups
-// per CU.  FSTAMD_BFS_TINY=0 turns the LDS tiers off, FSTAMD_GRAPH_GRID caps the grid.
-hipError_t DeviceEngine::run_bfs_ladder(uint32_t count, uint32_t* list, uint32_t* list2,
-                                        uint32_t* cnt, const int32_t* status,
-                                        const BfsLadder& L, hipStream_t stream, LhsRoute* route,
-                                        uint32_t* grid_out) {
-  const char* te = std::getenv("FSTAMD_BFS_TINY");
-  const bool tiny = L.tiny && !(te && std::strcmp(te, "0") == 0);
-  const bool replay = L.replay;
-  const uint32_t cap = grid_cap("FSTAMD_GRAPH_GRID");
-  for (int tier = tiny ? -2 : 0; count > 0; ++tier) {
-    const TinyCaps tc = tiny_caps(tier == -2 ? 1 : 2);
-    const BfsCaps c = tier < 0 ? BfsCaps{tc.n, tc.a, tc.h, tc.l, 0} : bfs_caps(tier);
-    const uint64_t fit = tier < 0 ? ~0ull : std::max<uint64_t>(1, kBfsBudget / c.stride);
-    if (kBfsBudget < c.stride) break;  // beyond the budget: those items stay OVERFLOW
-    const int kind = tier == -2 ? kLhsTierTiny128
-                     : tier == -1 ? kLhsTierTiny256
-                     : tier == 0 ? kLhsTierWave
-                                 : kLhsTierWG;
-    const uint64_t per_cu = tier < 0 ? (uint64_t)L.per_cu(kind)
-                            : tier == 0 ? 4 * FSTAMD_BFS_WAVES64
-                                        : 1;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(
-        {(uint64_t)count, (uint64_t)num_cus_ * per_cu, fit, (uint64_t)cap});
-    BfsWs ws{};
-    ws.slab = tier < 0 ? nullptr : (uint8_t*)scratch(kBfsSlab, (size_t)grid * c.stride);
-    ws.hdr = (uint32_t*)scratch(kBfsHdr, (size_t)grid * 8 * 4);
-    if ((tier >= 0 && !ws.slab) || !ws.hdr) return hipErrorOutOfMemory;
-    ws.stride = c.stride;
-    ws.ncap = c.ncap;
-    ws.acap = c.acap;
-    ws.hcap = c.hcap;
-    ws.lcap = c.lcap;
-    ws.wd_ticks = watchdog_ticks();
-    ws.lattice_only = L.lattice_only;
-    ws.lazy = 0;
-    ws.prof = nullptr;
-    if (replay) {  // heap + settled flags per workgroup (kernels/eager_bfs.hpp)
-      ws.replay =
-          (uint8_t*)scratch(kBfsHeap, (size_t)grid * ((size_t)(c.acap + 1) * 16 + c.ncap));
-      if (!ws.replay) return hipErrorOutOfMemory;
-    }
-    HIP_TRY(hipMemsetAsync(cnt + 1, 0, 8, stream));  // item counter + next list count
-    HIP_TRY(L.launch(kind, ws, cnt + 1, list, cnt, grid));
-    route->t[std::min(tier + 2, 3)] += count;
-    route->tiers_run += 1;
-    if (grid_out) *grid_out = std::max(*grid_out, grid);
-    collect_list_kernel<<<(count + 255) / 256, 256, 0, stream>>>(list, cnt, status,
-                                                                 kPathOverflow, list2, cnt + 2);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&count, cnt + 2, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(cnt, cnt + 2, 4, hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    std::swap(list, list2);
-  }
-  return hipSuccess;
 }
 
 hipError_t DeviceEngine::run_lhs_batch(const DeviceFst& rhs, const ChainInput& in,
@@ -2813,32 +2826,30 @@ hipError_t DeviceEngine::run_lhs_batch(const DeviceFst& rhs, const ChainInput& i
   const uint32_t num = in.num_strings;
   unsigned int* counter = (unsigned int*)scratch(kCounter, kCounterBytes);
   if (!counter) return hipErrorOutOfMemory;
-  HIP_TRY(hipMemsetAsync(counter, 0, 64, stream));
+  HIP_TRY(hipMemsetAsync(counter, 0, kCtrPrologueWords * 4, stream));
   HIP_TRY(hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), stream));
   if (num == 0) return hipSuccess;
   // every item starts as INTERNAL: an item no kernel finished can never read as a result
   HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out.status, kPathInternal, num, stream));
   LhsRoute r;
   uint32_t grid = 0;
-  if (stats) {
-    stats->engine = semantics == 0 ? 8 : 9;  // (7 is the lazy pull tier)
-    HIP_TRY(hipEventRecord(ev0_, stream));
-  }
-  if (semantics == 1) {
-    r.replay = num_replay;
-    HIP_TRY(run_lhs_eager(rhs, in, lhs, n, items_nonneg, num_nonneg, false, out, stream, &r,
-                          &grid));
-    HIP_TRY(run_lhs_eager(rhs, in, lhs, n, items_replay, num_replay, true, out, stream, &r,
-                          &grid));
-  } else {
+  if (stats) stats->engine = semantics == 0 ? 8 : 9;  // (7 is the lazy pull tier)
+  HIP_TRY(timed(stats, stream, [&]() -> hipError_t {
+    if (semantics == 1) {
+      r.replay = num_replay;
+      HIP_TRY(run_lhs_eager(rhs, in, lhs, n, items_nonneg, num_nonneg, false, out, stream, &r,
+                            &grid));
+      return run_lhs_eager(rhs, in, lhs, n, items_replay, num_replay, true, out, stream, &r,
+                           &grid);
+    }
     // table tiers of 1024 tuples x16 up to the single call's 2^26, each over the list of the
-    // items the previous one reported OVERFLOW ([6] item counter, [7] / [9] list counts)
+    // items the previous one reported OVERFLOW
     uint32_t* cur = (uint32_t*)scratch(kItems, (size_t)num * 4);
     uint32_t* nxt = (uint32_t*)scratch(kItems2, (size_t)num * 4);
     if (!cur || !nxt) return hipErrorOutOfMemory;
-    unsigned int* ic = counter + 6;
-    unsigned int* cur_cnt = counter + 7;
-    unsigned int* nxt_cnt = counter + 9;
+    unsigned int* ic = counter + kCtrLhsLazyItem;
+    unsigned int* cur_cnt = counter + kCtrLhsLazyListA;
+    unsigned int* nxt_cnt = counter + kCtrLhsLazyListB;
     uint32_t todo = num;
     const uint32_t* list = nullptr;  // the first tier takes every item
     int t = 0;
@@ -2852,26 +2863,18 @@ hipError_t DeviceEngine::run_lhs_batch(const DeviceFst& rhs, const ChainInput& i
       r.tiers_run += 1;
       grid = std::max(grid, g);
       HIP_TRY(hipMemsetAsync(nxt_cnt, 0, 4, stream));
-      if (list) {
-        collect_list_kernel<<<(todo + 255) / 256, 256, 0, stream>>>(
-            list, cur_cnt, out.status, kPathOverflow, nxt, nxt_cnt);
-      } else {
-        collect_status2_kernel<<<(num + 255) / 256, 256, 0, stream>>>(
-            out.status, num, kPathOverflow, kPathOverflow, nxt, nxt_cnt);
-      }
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(&todo, nxt_cnt, 4, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
+      HIP_TRY(hand_on(list ? from_list(list, cur_cnt, todo)
+                           : with_status2(num, kPathOverflow, kPathOverflow),
+                      out.status, nxt, nxt_cnt, &todo, stream));
       std::swap(cur, nxt);
       std::swap(cur_cnt, nxt_cnt);
       list = cur;
     }
-  }
+    return hipSuccess;
+  }));
   if (stats) {
     stats->grid = grid;
     stats->launches = 2 * r.tiers_run;  // each tier: its kernel and the hand-over list
-    HIP_TRY(hipEventRecord(ev1_, stream));
-    HIP_TRY(finish_stats(ev0_, ev1_, stats));
   }
   if (std::getenv("FSTAMD_ROUTE_LOG")) {
     if (semantics == 1)
@@ -2900,12 +2903,12 @@ hipError_t DeviceEngine::run_lattice_batch(const DeviceFst& rhs, const ChainInpu
   HIP_TRY(hipSetDevice(dev_));
   const uint32_t num = in.num_strings;
   const bool chain = lhs == nullptr;
-  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);  // [8..11], as run_bfs_chain
+  unsigned int* ctr = (unsigned int*)scratch(kCounter, kCounterBytes);
   uint32_t* list = (uint32_t*)scratch(kBfsList, (size_t)num * 4);
   uint32_t* list2 = (uint32_t*)scratch(kBfsList2, (size_t)num * 4);
   LatticeOutDev* d_lat = (LatticeOutDev*)scratch(kLatDesc, sizeof(LatticeOutDev));
   if (!ctr || !list || !list2 || !d_lat) return hipErrorOutOfMemory;
-  HIP_TRY(hipMemsetAsync(ctr, 0, 64, stream));
+  HIP_TRY(hipMemsetAsync(ctr, 0, kCtrPrologueWords * 4, stream));  // the ladder's words too
   HIP_TRY(hipMemsetAsync(lat.cursor, 0, 2 * sizeof(unsigned long long), stream));
   LhsRoute r;
   uint32_t grid_max = 0;
@@ -2927,31 +2930,28 @@ hipError_t DeviceEngine::run_lattice_batch(const DeviceFst& rhs, const ChainInpu
   // descriptor says so too)
   HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out.status, rhs.nan ? kPathUnsupported : kPathInternal,
                             num, stream));
-  if (stats) HIP_TRY(hipEventRecord(ev0_, stream));
-  uint32_t* cnt = ctr + 8;
-  uint32_t count = rhs.nan ? 0u : num;
-  if (count) {
-    collect_status2_kernel<<<(num + 255) / 256, 256, 0, stream>>>(out.status, num, kPathInternal,
-                                                                  kPathInternal, list, cnt);
-    HIP_TRY(hipGetLastError());
-  }
-  const GraphInput none{};
-  BfsLadder L;
-  L.tiny = true;
-  L.replay = false;
-  L.lattice_only = 1;
-  L.per_cu = [chain](int kind) { return lattice_per_cu(kind, chain); };
-  L.launch = [&](int kind, const BfsWs& ws, unsigned int* next_item, const uint32_t* cur,
-                 const uint32_t* cur_count, uint32_t grid) {
-    return launch_lattice(kind, chain, rhs.view, in, chain ? none : *lhs, next_item, cur,
-                          cur_count, ws, out, grid, stream);
-  };
-  HIP_TRY(run_bfs_ladder(count, list, list2, cnt, out.status, L, stream, &r, &grid_max));
+  HIP_TRY(timed(stats, stream, [&]() -> hipError_t {
+    uint32_t* cnt = ctr + kCtrBfsCount;
+    const uint32_t count = rhs.nan ? 0u : num;
+    // (every item, on the device alone: the host knows the count)
+    if (count)
+      HIP_TRY(collect(with_status2(num, kPathInternal, kPathInternal), out.status, list, cnt,
+                      stream));
+    const GraphInput none{};
+    BfsLadder L;
+    L.lattice_only = 1;
+    L.grid_cap = grid_cap("FSTAMD_GRAPH_GRID");
+    L.per_cu = [chain](int kind) { return lattice_per_cu(kind, chain); };
+    L.launch = [&](int kind, const BfsWs& ws, unsigned int* next_item, const uint32_t* cur,
+                   const uint32_t* cur_count, uint32_t grid) {
+      return launch_lattice(kind, chain, rhs.view, in, chain ? none : *lhs, next_item, cur,
+                            cur_count, ws, out, grid, stream);
+    };
+    return run_bfs_ladder(count, list, list2, cnt, out.status, L, stream, &r, &grid_max);
+  }));
   if (stats) {
     stats->grid = grid_max;
     stats->launches = 2 * r.tiers_run;  // each tier: its kernel and the hand-over list
-    HIP_TRY(hipEventRecord(ev1_, stream));
-    HIP_TRY(finish_stats(ev0_, ev1_, stats));
   }
   if (std::getenv("FSTAMD_ROUTE_LOG"))
     std::fprintf(stderr,

@@ -691,6 +691,21 @@ class DeviceEngine {
 
  private:
   explicit DeviceEngine(int dev);
+  // The stats bracket: ev0_, body() (a callable returning hipError_t), ev1_, kernel_ms.
+  template <class F>
+  hipError_t timed(LaunchStats* stats, hipStream_t stream, F&& body);
+  // run_chain's routes (device_engine.hip chain_route): run_chain's arguments and the counter
+  // block, its prologue words zeroed.  lazy_lds_sizes: the LDS replays at the head of the dense
+  // route; (*todo, *todo_n) = the device list of the strings they left OVERFLOW and its length.
+#define FSTAMD_ROUTE_ARGS                                                                      \
+  const DeviceFst &rhs, const ChainInput &in, uint32_t n, const BatchOutDev &out,              \
+      hipStream_t stream, LaunchStats *stats, unsigned int *counter
+  hipError_t route_eager_tiers(FSTAMD_ROUTE_ARGS);
+  hipError_t route_lazy_dense(FSTAMD_ROUTE_ARGS);
+  hipError_t route_lazy_rounds(FSTAMD_ROUTE_ARGS);
+  hipError_t route_lazy_hashed(FSTAMD_ROUTE_ARGS);
+  hipError_t lazy_lds_sizes(FSTAMD_ROUTE_ARGS, const uint32_t** todo, uint32_t* todo_n);
+#undef FSTAMD_ROUTE_ARGS
   hipStream_t stream_ = nullptr;   // the engine's own stream (non-blocking)
   bool after_pull_ = false;        // run_chain: the pull tier already ran (set_after_pull)
   void take_scratch(std::vector<void*>* out);  // an idle engine's workspaces, to be freed
@@ -743,16 +758,23 @@ class DeviceEngine {
                            const BatchOutDev& out, hipStream_t stream, LhsRoute* route,
                            uint32_t* grid_out);
   // The tier ladder of the general BFS engine over a device item list (LDS 128, LDS 256, tier
-  // 0 with one wave per item, then 256-thread tiers x8; OVERFLOW items move on), shared by
-  // run_lhs_eager and run_lattice_batch, which differ in the kernel a tier launches.
+  // 0, then 256-thread tiers x8; OVERFLOW items move on), shared by run_bfs_chain,
+  // run_lhs_eager and run_lattice_batch, which differ in the kernel a tier launches (`kind`:
+  // an LhsTier shape).
   struct BfsLadder {
-    bool tiny = true;           // start at the LDS tiers
+    int first = -2;             // first tier: -2 / -1 (LDS 128 / 256 tuples) or 0 (HBM)
     bool replay = false;        // heap-replay workspaces
+    bool lazy = false;          // BfsWs::lazy
+    bool wg0 = false;           // tier 0 as kLhsTierWG (256 threads, 4 per CU), not one wave
+    bool prof = false;          // FSTAMD_BFS_PROF: the phase profile, one line per tier
     uint32_t lattice_only = 0;  // BfsWs::lattice_only
+    uint32_t grid_cap = 0xFFFFFFFFu;      // FSTAMD_GRAPH_GRID of the batches
     std::function<int(int kind)> per_cu;  // resident workgroups per CU of an LDS tier
     std::function<hipError_t(int kind, const BfsWs& ws, unsigned int* next_item,
                              const uint32_t* list, const uint32_t* count_dev, uint32_t grid)>
         launch;
+    // optional, after a tier's hand-over: the items it took and those it handed on
+    std::function<void(int tier, uint32_t count_in, uint32_t count_out)> after;
   };
   hipError_t run_bfs_ladder(uint32_t count, uint32_t* list, uint32_t* list2, uint32_t* cnt,
                             const int32_t* status, const BfsLadder& L, hipStream_t stream,

@@ -945,7 +945,7 @@ __device__ void sp_replay(const BfsTables& T, uint32_t n_nodes, uint32_t n_arcs,
 // utterance on average) keep every table in LDS instead of an HBM slab, so a BFS level
 // costs LDS round trips rather than HBM ones, and no string clears a 384 KB HBM hash.
 // Strings that outgrow it report OVERFLOW and move on to tier 0.  The caps are the
-// host's ws.* values for this tier (device_engine.hip run_bfs_chain).
+// host's ws.* values for this tier (device_engine.hip run_bfs_ladder).
 // Two sizes (config 4's lattices: at most 87 / 159 tuples, 1.0-1.3 arcs per tuple, and up
 // to ~150 BFS levels: a verbalizer word is an epsilon chain of 3-5 levels; what outgrows the
 // first size finishes in the second rather than in HBM):

@@ -1,6 +1,6 @@
 // lattice_batch.hip -- the lattice batch (fst_compose_frozen_batch and its lhs and device
 // forms): the emitting instances of eager_bfs_kernel (kernels/eager_bfs.hpp, kEmit: chain and
-// kLhsBatch lhs at the four tier shapes of run_lhs_eager / run_bfs_chain), their launches, and
+// kLhsBatch lhs at the four tier shapes of run_bfs_ladder), their launches, and
 // the compaction of the arena into FstLhsBatch's layout in item order, the lattice twin of
 // compact_paths.  DeviceEngine::run_lattice_batch / compact_lattices (device_engine.hip) drive
 // them.

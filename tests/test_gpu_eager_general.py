@@ -285,3 +285,48 @@ def test_batch_tiny_tier_off_matches(monkeypatch, env):
     assert np.array_equal(a.ilabels, b.ilabels) and np.array_equal(a.olabels, b.olabels)
     assert np.array_equal(a.weights.view(np.uint64), b.weights.view(np.uint64))
     assert np.array_equal(a.finals.view(np.uint64), b.finals.view(np.uint64))
+
+
+@pytest.mark.parametrize("sem", ["eager", "lazy_rounds"])
+def test_batch_tier0_256_threads(monkeypatch, capfd, sem):
+    # the ladder's tier 0 as a 256-thread workgroup (FSTAMD_BFS_WG0=256) with the LDS tiers off
+    # (FSTAMD_BFS_TINY=0): tier 0 takes every string with that instance.  Eager on an rhs with
+    # input epsilons (the general engine takes every string); lazy on finite weights >= 0
+    # through the rounds route, which reaches the ladder with the lazy flag set.  Bit-exact
+    # against the oracle; the phase profile's line per tier (FSTAMD_BFS_PROF) says which
+    # instance ran: tier 0 alone, with 256 threads.
+    monkeypatch.setenv("FSTAMD_BFS_PROF", "1")
+    monkeypatch.setenv("FSTAMD_BFS_WG0", "256")
+    monkeypatch.setenv("FSTAMD_BFS_TINY", "0")
+    if sem == "lazy_rounds":
+        monkeypatch.setenv("FSTAMD_LAZY_ENGINE", "rounds")
+    rng = np.random.default_rng(8300)
+    f = random_rhs(rng, 25, 90, 4, eps=True, frac=True)
+    seqs = [[int(x) for x in rng.integers(1 if i % 5 else 0, 5, int(rng.integers(0, 13)))]
+            for i in range(64)]
+    check(O.freeze(f), *csr(seqs), LAZY if sem == "lazy_rounds" else EAGER)
+    assert F.last_launch_stats().engine == (3 if sem == "lazy_rounds" else 2)
+    prof = [x for x in capfd.readouterr().err.splitlines() if x.startswith("[bfs prof]")]
+    assert len(prof) == 1 and prof[0].startswith("[bfs prof] tier 0 grid ") and \
+        " wg 256 items " in prof[0], prof
+
+
+def test_batch_negative_weights_start_at_tier0(monkeypatch):
+    # the heap-replay route (negative weights) through the chain entry: its heap lives in HBM,
+    # so the ladder starts at tier 0 whether FSTAMD_BFS_TINY is unset or 0 -- the LDS tiers
+    # have no replay workspace and would not give the reference's heap order.  Both runs match
+    # the oracle bit for bit, CYCLE statuses included, and each other.
+    rng = np.random.default_rng(6400)
+    f = negative_graph(rng, 24, 100, True)
+    blob = O.freeze(f)
+    seqs = [[int(x) for x in rng.integers(0 if i % 7 == 0 else 1, 5, int(rng.integers(0, 10)))]
+            for i in range(64)]
+    monkeypatch.delenv("FSTAMD_BFS_TINY", raising=False)
+    a, _ = check(blob, *csr(seqs), EAGER)
+    assert F.last_launch_stats().engine == 6
+    monkeypatch.setenv("FSTAMD_BFS_TINY", "0")
+    b, _ = check(blob, *csr(seqs), EAGER)
+    assert F.last_launch_stats().engine == 6
+    assert np.array_equal(a.status, b.status) and np.array_equal(a.offsets, b.offsets)
+    assert np.array_equal(a.olabels, b.olabels)
+    assert np.array_equal(bits(a.weights), bits(b.weights))

@@ -1,4 +1,4 @@
-"""GPU parity of every tier of the eager layered chain (device_engine.hip run_chain).
+"""GPU parity of every tier of the eager layered chain (device_engine.hip route_eager_tiers).
 
 The chain is P (pull over the reverse mirror, eager_pull.hpp) -> A0 (direct-mapped
 window, eager_window.hpp) -> A (hashed wave, eager_wave.hpp) -> B (256-thread LDS tables)
