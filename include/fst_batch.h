@@ -465,6 +465,16 @@ uint64_t fst_debug_text_compact(uint32_t num_strings, uint64_t* offsets, const u
 void fst_debug_expand_weight_codes(const uint8_t* codes, uint64_t n, const double* table,
                                    double* dst);
 
+/* Diagnostics / tests, no GPU needed: the streamed batch's part planner.  offsets[0 ..
+ * num_strings] = a shard's label offsets (any first offset), per_mille[0 .. num_per_mille) =
+ * the fractions of its labels to cut at (each in 1..999, as FSTAMD_STREAM_CUTS gives them).
+ * Writes the parts' string boundaries 0, .., num_strings into cuts (room for num_per_mille + 2)
+ * and returns how many it wrote: 2 (one part) for a shard under 2^15 strings or 2^22 labels;
+ * a cut is kept only past the previous one and before num_strings.  0 on a null argument. */
+uint32_t fst_debug_stream_part_cuts(const uint64_t* offsets, uint32_t num_strings,
+                                    const uint64_t* per_mille, uint32_t num_per_mille,
+                                    uint32_t* cuts);
+
 #ifdef __cplusplus
 }
 #endif

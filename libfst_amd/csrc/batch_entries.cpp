@@ -815,6 +815,16 @@ void fst_debug_expand_weight_codes(const uint8_t* codes, uint64_t n, const doubl
   expand_weight_codes(codes, (size_t)n, table, dst);
 }
 
+uint32_t fst_debug_stream_part_cuts(const uint64_t* offsets, uint32_t num_strings,
+                                    const uint64_t* per_mille, uint32_t num_per_mille,
+                                    uint32_t* cuts) {
+  if (!offsets || !cuts || (num_per_mille && !per_mille)) return 0;
+  const std::vector<uint32_t> c = stream_part_cuts(
+      offsets, num_strings, std::vector<uint64_t>(per_mille, per_mille + num_per_mille));
+  std::copy(c.begin(), c.end(), cuts);
+  return (uint32_t)c.size();
+}
+
 int32_t fst_weight_type(FstHandle b) {
   auto f = frozen_get(b);
   return f ? (int32_t)f->weight_type() : -1;

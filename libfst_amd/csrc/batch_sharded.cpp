@@ -3,7 +3,6 @@
 // one-device batch, and the per-shard compute steps (pipeline stages, text, general lhs,
 // pipelines on a general first stage, and the lattice batch with its own arena).
 #include <cmath>
-#include <condition_variable>
 
 #include "host_rt.hpp"
 
@@ -558,35 +557,23 @@ FstError run_pipelined(int dev, FrozenFst& b, const uint32_t* labels, const uint
   // is staged through pinned memory on the copying thread), so sub-shard j + 1's upload
   // runs while sub-shard j computes; the engine's stream waits on each upload's event.
   struct Uploader : OwnStream {  // (the thread joined before the stream goes)
-    std::mutex mu;
-    std::condition_variable cv;
-    uint32_t ready = 0;
-    bool failed = false;
-    std::thread th;
-    ~Uploader() {
-      if (th.joinable()) th.join();
-    }
+    PartGate gate;
+    ThreadGroup th;
   } U;
   if (hipStreamCreateWithFlags(&U.s, hipStreamNonBlocking) != hipSuccess) return FST_OOM;
   U.ev.assign(parts, nullptr);
   for (uint32_t j = 0; j < parts; ++j)
     if (hipEventCreateWithFlags(&U.ev[j], hipEventDisableTiming) != hipSuccess) return FST_OOM;
-  U.th = std::thread([&, dev] {
+  U.th.add([&, dev] {
     bool ok = hipSetDevice(dev) == hipSuccess;
-    for (uint32_t j = 0; j < parts; ++j) {
+    for (uint32_t j = 0; j < parts && ok; ++j) {
       const uint64_t a = rebased[sh[j].s0], z = rebased[sh[j].s1];
       ok = ok && (z == a || hipMemcpyAsync((uint32_t*)d_lab.p + a, labels + offsets[0] + a,
                                            (z - a) * 4, hipMemcpyHostToDevice, U.s) == hipSuccess);
       ok = ok && hipEventRecord(U.ev[j], U.s) == hipSuccess;
-      std::lock_guard<std::mutex> g(U.mu);
-      if (!ok) {
-        U.failed = true;
-        U.cv.notify_all();
-        return;
-      }
-      U.ready = j + 1;
-      U.cv.notify_all();
+      if (ok) U.gate.publish(j + 1);
     }
+    if (!ok) U.gate.fail();
   });
   if (t_prof) t_prof->lap(0);
   if (!alloc_result(out, num, total)) return FST_OOM;  // paths of L arcs: <= total arcs
@@ -596,11 +583,7 @@ FstError run_pipelined(int dev, FrozenFst& b, const uint32_t* labels, const uint
   uint64_t base = 0;
   for (uint32_t j = 0; j < parts; ++j) {
     Shard& S = sh[j];
-    {
-      std::unique_lock<std::mutex> g(U.mu);
-      U.cv.wait(g, [&] { return U.failed || U.ready > j; });
-      if (U.failed) return FST_OOM;
-    }
+    if (!U.gate.wait_for(j)) return FST_OOM;
     if (hipStreamWaitEvent(stream, U.ev[j], 0) != hipSuccess) return FST_OOM;
     uint32_t ml = 0;
     for (uint32_t i = S.s0; i < S.s1; ++i) ml = std::max<uint32_t>(ml, (uint32_t)(rebased[i + 1] - rebased[i]));

@@ -18,7 +18,7 @@
 // Labels read from host memory instead (zero-copy) measured 34.5 vs 30.6 ms per 1M metric
 // strings: a PCIe read at every string's start.  Returns kStreamNotApplicable when the mode
 // does not apply; the caller then takes the pipelined path.
-#include <condition_variable>
+#include <atomic>
 #include <map>
 
 #include "host_rt.hpp"
@@ -27,32 +27,6 @@
 namespace fstamd::host {
 namespace {
 
-// FSTAMD_STREAM_CODES: 0 = the f64 copy-out for every part, 1 = every part's weights leave
-// as 1-B codes (default), 2 = every part but the last
-int stream_codes_mode() {
-  const char* e = std::getenv("FSTAMD_STREAM_CODES");
-  const int m = e ? std::atoi(e) : 1;
-  return m < 0 || m > 2 ? 1 : m;
-}
-
-// The parts' cuts, per mille of a shard's labels: FSTAMD_STREAM_CUTS, or 1/43 and 7/43 (each
-// part's upload fits in the previous part's compute), and, when every part leaves codes,
-// shrinking parts after the big one, so that little expansion is left after the last kernel.
-std::vector<uint64_t> stream_cuts(bool all_coded) {
-  std::vector<uint64_t> pm{23, 163};
-  if (all_coded) pm = {23, 163, 700, 900, 970};
-  if (const char* ce = std::getenv("FSTAMD_STREAM_CUTS")) {
-    pm.clear();
-    for (const char* q = ce; *q;) {
-      char* e = nullptr;
-      const unsigned long v = std::strtoul(q, &e, 10);
-      if (e == q) break;
-      if (v > 0 && v < 1000) pm.push_back(v);
-      q = *e ? e + 1 : e;
-    }
-  }
-  return pm;
-}
 constexpr size_t kStreamMaxParts = 64;
 
 // a block of the pinned host pool, given back on scope exit
@@ -147,144 +121,194 @@ struct StreamShard {
   uint32_t launches = 0;
 };
 
-FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const uint64_t* poff,
-                      uint32_t max_len, uint32_t n, int semantics, int32_t* first_all,
-                      std::mutex* later_mu) {
+// One run of stream_shard: what the shard owns, and the phases stream_shard calls in order.
+//
+// The order of the owning members below is the lifetime contract.  Members go in reverse, so
+// every return of every phase
+//   1. aborts the expanders' gate and joins them (a recorded part is still expanded),
+//   2. joins the uploader and the ilabel copiers (the second engine's driver never outlives
+//      drive_parts),
+//   3. drains `up`, `sA` and `sB`: no kernel or copy still uses the buffers or the result,
+//   4. releases txs, the text-mode buffers, the code arena and the device buffers,
+//   5. the engine leases,
+//   6. the part cuts, the pinned staging block and the shard's own offsets,
+//   7. the stream kit,
+//   8. and last the per-device later_mu lock: the later tiers of the shards of one device run
+//      one shard at a time, each to the end of its leases (the heavy replays size their
+//      workspaces from the free HBM, which a concurrent shard's would have taken).
+// A new owner goes where its users come after it and what it uses comes before it.
+struct ShardRun {
+  // ---- the call ----
+  StreamShard& S;
+  DeviceFst& D;
+  const StreamIo& io;
+  const StreamKnobs& knobs;
+  const uint64_t* const poff;
+  const uint32_t max_len, n;
+  const int semantics;
   const bool tm = io.text_mode();
   FstBatchResult* const out = io.out;  // (label mode)
-  // the later tiers of the shards of one device run one shard at a time, each to the end of
-  // its leases (declared after this lock, so released before it): the heavy replays size
-  // their workspaces from the free HBM, which a concurrent shard's would have taken
-  std::unique_lock<std::mutex> later_lock(*later_mu, std::defer_lock);
   const int dev = S.dev;
-  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
   const uint32_t num = S.s1 - S.s0;
   const uint64_t lbase = poff[S.s0], total = poff[S.s1] - lbase;
-  if (num == 0) return FST_OK;
-  KitLease K(dev);
-  if (!K) return FST_OOM;
-  const hipStream_t up = K->up;
-  // the shard's offsets from its first label (shard 0 of the batch: poff itself)
-  PinnedVec<uint64_t> loff_own(lbase ? num + 1 : 0);
-  const uint64_t* loff = poff + S.s0;
-  if (lbase) {
-    for (uint32_t i = 0; i <= num; ++i) loff_own[i] = poff[S.s0 + i] - lbase;
-    loff = loff_own.data();
-  }
-  const uint32_t* lsrc = io.labels ? io.labels + lbase : nullptr;
-  const uint8_t* tsrc = io.text ? io.text + lbase : nullptr;
+  const uint32_t* const lsrc = io.labels ? io.labels + lbase : nullptr;
+  const uint8_t* const tsrc = io.text ? io.text + lbase : nullptr;
   uint32_t* const il_out = tm ? nullptr : out->ilabels + lbase;
-  struct Threads {  // joined on every return (declared after what they use)
-    std::vector<std::thread> th;
-    void join() {
-      for (auto& t : th) t.join();
-      th.clear();
-    }
-    ~Threads() { join(); }
-  };
+  int32_t* const st_out = (tm ? io.tout->status : out->status) + S.s0;
+  // (text mode: the total weights in the final weights' place)
+  double* const fin_out = (tm ? io.tout->total_weight : out->final_weights) + S.s0;
+  int32_t* const first;  // the pull tier's statuses
+  // ---- the plan ----
+  const uint64_t* loff = poff + S.s0;  // the shard's offsets from its first label
+  double code_table[256];
+  int codes_mode = 0;
+  size_t parts = 0, ncoded = 0;  // parts [0, ncoded) leave codes
+  hipStream_t up = nullptr, sA = nullptr, sB = nullptr;
+  BatchOutDev vb{};
+  uint32_t launches = 0;
+  std::chrono::steady_clock::time_point tk0, tx0;  // the parts' and the expanders' start
+  // ---- the owners, in the order of the contract ----
+  std::unique_lock<std::mutex> later_lock;
+  KitLease K;
+  PinnedVec<uint64_t> loff_own;  // (shard 0 of the batch reads poff itself)
+  PinBlock staging;              // the shard's codes, indexed like its labels
+  std::vector<uint32_t> cut;
+  DeviceEngine::Lease EA, EB;
+  // (text mode: d_lab holds the bytes themselves; d_ctr: an item counter per part)
+  std::unique_ptr<DevBuf> d_lab, d_off, d_first, d_ctr;
+  std::unique_ptr<DevOut> o;
+  std::unique_ptr<DevBuf> d_codes;  // the device byte arena of the codes (indexed like the path arena)
+  // text mode: byte counts and total weights per string, and one TextOutDev per part (the
+  // kernels reach it through BatchOutDev::text), uploaded with the offsets
+  // (d_lab4: the widened labels of a shard that hands strings on, allocated only then)
+  std::unique_ptr<DevBuf> d_nb, d_tw, d_tx, d_lab4;
+  std::vector<TextOutDev> txs;
+  StreamDrain drain{{nullptr, nullptr, nullptr}};
+  PartGate uploaded;
+  ThreadGroup uploads;
+  RecordedGate recorded;
+  std::atomic<bool> x_failed{false};
+  std::vector<double> x_ev, x_end;  // [thread * ncoded + part] (FSTAMD_HOST_PROF)
+  std::vector<FstError> perr;
+  ThreadGroup expanders{&recorded};
 
-  // ---- parts: string ranges cut at these fractions of the labels (per mille; small
-  // shards: one part; stream_cuts).  FSTAMD_STREAM_CUTS overrides (A/B, one box, f64
-  // copy-out: "23,163" 30.9 ms per 1M metric strings, "167" 31.2, "100,400" 31.0, "125"
-  // 31.5) ----
+  ShardRun(StreamShard& S_, DeviceFst& D_, const StreamIo& io_, const StreamKnobs& knobs_,
+           const uint64_t* poff_, uint32_t max_len_, uint32_t n_, int semantics_,
+           int32_t* first_all, std::mutex* later_mu)
+      : S(S_), D(D_), io(io_), knobs(knobs_), poff(poff_), max_len(max_len_), n(n_),
+        semantics(semantics_), first(first_all + S_.s0), later_lock(*later_mu, std::defer_lock),
+        K(S_.dev) {}
+
+  double x_ms() const {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tx0).count();
+  }
+
+  // Phase 1.  Decides the weight-code mode and the parts; owns the staging block afterwards.
+  //
+  // Parts: string ranges cut at fractions of the labels (stream_part_cuts, StreamKnobs::cuts).
+  // FSTAMD_STREAM_CUTS overrides (A/B, one box, f64 copy-out: "23,163" 30.9 ms per 1M metric
+  // strings, "167" 31.2, "100,400" 31.0, "125" 31.5).
   // Weight codes: when this rhs, these semantics and this max_len take tier
   // P's code instances (pull_codes_table: pull_rk / pull_pack decide) the coded parts' weights
   // cross the link as one byte per arc into a pinned staging block, and expander threads turn
   // each part's codes into the result's f64 weights once that part's completion event has
   // passed, while the later parts run.  The last part's expansion stands exposed after the
   // last kernel, so the coded route ends on shrinking parts.
-  double code_table[256];
-  int codes_mode = tm ? 0 : stream_codes_mode();
-  if (codes_mode && !pull_codes_table(D, semantics, max_len, code_table)) codes_mode = 0;
-  PinBlock staging;  // the shard's codes, indexed like its labels
-  if (codes_mode) {
-    staging.reset(pin_alloc(std::max<uint64_t>(total, 1)));  // (the copy-out stays inside each string)
-    if (!staging.p || !pin_is_pinned(staging.p)) {  // (the pool gave pageable memory)
-      staging.reset(nullptr);
-      codes_mode = 0;
+  FstError plan() {
+    if (!K) return FST_OOM;
+    up = K->up;
+    if (lbase) {
+      loff_own.resize(num + 1);
+      for (uint32_t i = 0; i <= num; ++i) loff_own[i] = poff[S.s0 + i] - lbase;
+      loff = loff_own.data();
     }
-  }
-  std::vector<uint32_t> cut{0};
-  if (total >= (1u << 22) && num >= (1u << 15)) {
-    for (uint64_t f : stream_cuts(codes_mode == 1)) {
-      const uint64_t want = total * f / 1000;
-      const uint32_t i = (uint32_t)(std::upper_bound(loff, loff + num, want) - loff);
-      if (i > cut.back() && i < num) cut.push_back(i);
+    codes_mode = tm ? 0 : knobs.codes_mode;
+    if (codes_mode && !pull_codes_table(D, semantics, max_len, code_table)) codes_mode = 0;
+    if (codes_mode) {
+      staging.reset(pin_alloc(std::max<uint64_t>(total, 1)));  // (the copy-out stays inside each string)
+      if (!staging.p || !pin_is_pinned(staging.p)) {  // (the pool gave pageable memory)
+        staging.reset(nullptr);
+        codes_mode = 0;
+      }
     }
+    cut = stream_part_cuts(loff, num, knobs.cuts(codes_mode == 1));
+    parts = cut.size() - 1;
+    // one upload event and one completion event a part (run_streamed has checked that this
+    // device's kit and events exist before it allocated the result)
+    if (parts > kStreamMaxParts || !K->events(2 * parts)) return FST_OOM;
+    // mode 2: the last part keeps the f64 copy-out
+    ncoded = codes_mode == 1 ? parts : codes_mode == 2 ? parts - 1 : 0;
+    if (knobs.route_log)
+      std::fprintf(stderr, "[libfst_amd route] stream: weight codes %s, mode %d, parts %zu\n",
+                   ncoded ? "on" : "off", ncoded ? codes_mode : 0, parts);
+    return FST_OK;
   }
-  cut.push_back(num);
-  const size_t parts = cut.size() - 1;
-  // one upload event and one completion event a part (run_streamed has checked that this
-  // device's kit and events exist before it allocated the result)
-  if (parts > kStreamMaxParts || !K->events(2 * parts)) return FST_OOM;
-  // parts [0, ncoded) leave codes; mode 2: the last part keeps the f64 copy-out
-  const size_t ncoded = codes_mode == 1 ? parts : codes_mode == 2 ? parts - 1 : 0;
-  if (std::getenv("FSTAMD_ROUTE_LOG"))
-    std::fprintf(stderr, "[libfst_amd route] stream: weight codes %s, mode %d, parts %zu\n",
-                 ncoded ? "on" : "off", ncoded ? codes_mode : 0, parts);
 
-  // ---- engines and device buffers ----
-  DeviceEngine::Lease EA = DeviceEngine::acquire(dev);
-  if (!EA) return FST_INVALID_ARG;
-  DeviceEngine::Lease EB;
-  if (parts > 1) EB = DeviceEngine::try_acquire(dev);  // (none free: one engine in order)
-  const hipStream_t sA = EA.stream(), sB = EB ? EB.stream() : nullptr;
-  // (text mode: d_lab holds the bytes themselves)
-  DevBuf d_lab(std::max<uint64_t>(total, 1) * (tm ? 1 : 4)), d_off((num + 1) * 8ull),
-      d_first(std::max<size_t>(num, 1) * 4ull), d_ctr(64 * 4);  // item counter per part
-  DevOut o(num, total + 4);
-  if (!d_lab.p || !d_off.p || !d_first.p || !d_ctr.p || !o.ok()) return FST_OOM;
-  // the device byte arena of the codes (indexed like the path arena)
-  std::unique_ptr<DevBuf> d_codes;
-  if (ncoded) {
-    d_codes = std::make_unique<DevBuf>(std::max<uint64_t>(total, 1));
-    if (!d_codes->p) return FST_OOM;
+  // Phase 2.  Leases the engines and allocates the device buffers; from here every return
+  // drains the three streams.
+  FstError acquire() {
+    EA = DeviceEngine::acquire(dev);
+    if (!EA) return FST_INVALID_ARG;
+    if (parts > 1) EB = DeviceEngine::try_acquire(dev);  // (none free: one engine in order)
+    sA = EA.stream();
+    sB = EB ? EB.stream() : nullptr;
+    d_lab = std::make_unique<DevBuf>(std::max<uint64_t>(total, 1) * (tm ? 1 : 4));
+    d_off = std::make_unique<DevBuf>((num + 1) * 8ull);
+    d_first = std::make_unique<DevBuf>(std::max<size_t>(num, 1) * 4ull);
+    d_ctr = std::make_unique<DevBuf>(64 * 4);
+    o = std::make_unique<DevOut>(num, total + 4);
+    if (!d_lab->p || !d_off->p || !d_first->p || !d_ctr->p || !o->ok()) return FST_OOM;
+    if (ncoded) {
+      d_codes = std::make_unique<DevBuf>(std::max<uint64_t>(total, 1));
+      if (!d_codes->p) return FST_OOM;
+    }
+    if (tm) {
+      d_nb = std::make_unique<DevBuf>(std::max<size_t>(num, 1) * 4ull);
+      d_tw = std::make_unique<DevBuf>(std::max<size_t>(num, 1) * 8ull);
+      d_tx = std::make_unique<DevBuf>(64 * sizeof(TextOutDev));
+      if (!d_nb->p || !d_tw->p || !d_tx->p) return FST_OOM;
+      for (size_t p = 0; p < parts; ++p)
+        txs.push_back(TextOutDev{io.tout->text + lbase, (uint32_t*)d_nb->p + cut[p],
+                                 (double*)d_tw->p + cut[p]});
+    }
+    // the arena's path arrays shifted so that each element shares its host twin's address
+    // modulo 16 (the copy-out's 16-B units, kernels/device_common.hpp copy_out_paths)
+    vb = o->v;
+    vb.out_il += lbase & 3u;
+    vb.out_ol += lbase & 3u;
+    vb.out_w += lbase & 1u;
+    drain.s[0] = up, drain.s[1] = sA, drain.s[2] = sB;
+    return FST_OK;
   }
-  // text mode: byte counts and total weights per string, and one TextOutDev per part (the
-  // kernels reach it through BatchOutDev::text), uploaded with the offsets
-  // (d_lab4: the widened labels of a shard that hands strings on, allocated only then)
-  std::unique_ptr<DevBuf> d_nb, d_tw, d_tx, d_lab4;
-  std::vector<TextOutDev> txs;  // (outlives the streams' work: declared before sync_all)
-  if (tm) {
-    d_nb = std::make_unique<DevBuf>(std::max<size_t>(num, 1) * 4ull);
-    d_tw = std::make_unique<DevBuf>(std::max<size_t>(num, 1) * 8ull);
-    d_tx = std::make_unique<DevBuf>(64 * sizeof(TextOutDev));
-    if (!d_nb->p || !d_tw->p || !d_tx->p) return FST_OOM;
-    for (size_t p = 0; p < parts; ++p)
-      txs.push_back(TextOutDev{io.tout->text + lbase, (uint32_t*)d_nb->p + cut[p],
-                               (double*)d_tw->p + cut[p]});
-  }
-  // the arena's path arrays shifted so that each element shares its host twin's address
-  // modulo 16 (the copy-out's 16-B units, kernels/device_common.hpp copy_out_paths)
-  BatchOutDev vb = o.v;
-  vb.out_il += lbase & 3u;
-  vb.out_ol += lbase & 3u;
-  vb.out_w += lbase & 1u;
-  // every return: no kernel or copy still uses the buffers or the result
-  StreamDrain sync_all{{up, sA, sB}};
 
-  // ---- uploads (offsets, then each part's labels: one event per part) ----
+  // Phase 3.  Starts the uploader (offsets, then each part's labels: one event per part) and
+  // the threads that copy the labels into the result's ilabels.
   // Two ways to move the labels (FSTAMD_STREAM_STAGE): 0 = the runtime stages the pageable
   // source itself while other threads copy it into the result's ilabels (the labels cross
   // host DRAM twice); 1 = threads copy each chunk into the result's (pinned) ilabels and
   // the chunk's DMA reads it from there (once).
-  const char* stage_env = std::getenv("FSTAMD_STREAM_STAGE");
-  const int stage_mode = stage_env ? std::atoi(stage_env) : 0;
-  struct Ready {
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t n = 0;
-    bool failed = false;
-  } R;
-  Threads Th;
-  Th.th.emplace_back([&] {
+  void start_uploads() {
+    uploads.add([this] { upload(); });
+    if (!tm && knobs.stage != 1) {
+      // the result's ilabels, once the uploads are staged: the runtime's staging copies of
+      // a pageable source read the same pages, and the kernels wait for them, not for these
+      const uint64_t T = total >= (1u << 20) ? 3 : 1;
+      for (uint64_t t = 0; t < T; ++t)
+        uploads.add([this, t, T] {
+          uploaded.wait_all(parts);
+          const uint64_t a = total * t / T, z = total * (t + 1) / T;
+          if (z > a) std::memcpy(il_out + a, lsrc + a, (z - a) * 4);
+        });
+    }
+  }
+  void upload() {
     // (the fills first, on the idle GPU: every string INTERNAL until a tier finishes it,
     // the parts' item counters zero; the parts wait on events recorded after them)
     bool ok = hipSetDevice(dev) == hipSuccess &&
-              hipMemsetD32Async((hipDeviceptr_t)o.status.p, kPathInternal, num, up) == hipSuccess &&
-              hipMemsetD32Async((hipDeviceptr_t)d_first.p, kPathInternal, num, up) == hipSuccess &&
-              hipMemsetAsync(d_ctr.p, 0, 64 * 4, up) == hipSuccess &&
-              hipMemcpyAsync(d_off.p, loff, (num + 1) * 8ull, hipMemcpyHostToDevice, up) ==
+              hipMemsetD32Async((hipDeviceptr_t)o->status.p, kPathInternal, num, up) == hipSuccess &&
+              hipMemsetD32Async((hipDeviceptr_t)d_first->p, kPathInternal, num, up) == hipSuccess &&
+              hipMemsetAsync(d_ctr->p, 0, 64 * 4, up) == hipSuccess &&
+              hipMemcpyAsync(d_off->p, loff, (num + 1) * 8ull, hipMemcpyHostToDevice, up) ==
                   hipSuccess &&
               (!tm || hipMemcpyAsync(d_tx->p, txs.data(), parts * sizeof(TextOutDev),
                                      hipMemcpyHostToDevice, up) == hipSuccess);
@@ -292,9 +316,9 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
     for (size_t p = 0; p < parts && ok; ++p) {
       const uint64_t a = loff[cut[p]], z = loff[cut[p + 1]];
       if (tm) {  // the part's bytes, as they are
-        ok = z == a || hipMemcpyAsync((uint8_t*)d_lab.p + a, tsrc + a, z - a,
+        ok = z == a || hipMemcpyAsync((uint8_t*)d_lab->p + a, tsrc + a, z - a,
                                       hipMemcpyHostToDevice, up) == hipSuccess;
-      } else if (stage_mode == 1) {
+      } else if (knobs.stage == 1) {
         for (uint64_t c = a; c < z && ok; c += kChunk) {
           const uint64_t e = std::min(z, c + kChunk), w = e - c;
           const uint64_t T = w >= (1u << 19) ? 4 : 1;
@@ -306,129 +330,81 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
             });
           std::memcpy(il_out + c, lsrc + c, (w / T) * 4);
           for (auto& x : cp) x.join();
-          ok = hipMemcpyAsync((uint32_t*)d_lab.p + c, il_out + c, w * 4, hipMemcpyHostToDevice,
+          ok = hipMemcpyAsync((uint32_t*)d_lab->p + c, il_out + c, w * 4, hipMemcpyHostToDevice,
                               up) == hipSuccess;
         }
       } else {
         // (a pageable source is staged through pinned memory before this returns)
-        ok = z == a || hipMemcpyAsync((uint32_t*)d_lab.p + a, lsrc + a, (z - a) * 4,
+        ok = z == a || hipMemcpyAsync((uint32_t*)d_lab->p + a, lsrc + a, (z - a) * 4,
                                       hipMemcpyHostToDevice, up) == hipSuccess;
       }
       ok = ok && hipEventRecord(K->ev[p], up) == hipSuccess;
-      std::lock_guard<std::mutex> g(R.mu);
-      if (ok) R.n = p + 1;
-      R.cv.notify_all();
+      if (ok) uploaded.publish(p + 1);
     }
-    std::lock_guard<std::mutex> g(R.mu);
-    if (!ok) R.failed = true;
-    R.cv.notify_all();
-  });
-  if (!tm && stage_mode != 1) {
-    // the result's ilabels, once the uploads are staged: the runtime's staging copies of
-    // a pageable source read the same pages, and the kernels wait for them, not for these
-    const uint64_t T = total >= (1u << 20) ? 3 : 1;
-    for (uint64_t t = 0; t < T; ++t)
-      Th.th.emplace_back([&, t, T] {
-        {
-          std::unique_lock<std::mutex> g(R.mu);
-          R.cv.wait(g, [&] { return R.failed || R.n == parts; });
-        }
-        const uint64_t a = total * t / T, z = total * (t + 1) / T;
-        if (z > a) std::memcpy(il_out + a, lsrc + a, (z - a) * 4);
-      });
+    if (!ok) uploaded.fail();
   }
 
-  // ---- the expanders: thread t of T takes the t-th slice of every coded part, in part
-  // order.  It waits (host side) until the part's completion event has been recorded --
-  // synchronising an event nobody recorded yet, or one a previous call left complete, would
-  // return at once -- then for the event itself, and only then reads the part's codes.
-  // Nothing polls memory the device writes.  Joined on every return (declared after the
-  // staging block, the result and the streams' drain). ----
-  struct Recorded {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<char> rec;
-    bool abort = false;
-  } X;
-  X.rec.assign(parts, 0);
-  auto x_abort = [&] {
-    std::lock_guard<std::mutex> g(X.mu);
-    X.abort = true;
-    X.cv.notify_all();
-  };
-  std::atomic<bool> x_failed{false};
-  // (FSTAMD_HOST_PROF: when each part's event passed and when its expansion ended, ms from
-  // the expanders' start, per thread)
-  const bool x_prof = std::getenv("FSTAMD_HOST_PROF") != nullptr;
-  const auto tx0 = std::chrono::steady_clock::now();
-  auto x_ms = [&] {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tx0).count();
-  };
-  std::vector<double> x_ev, x_end;  // [thread * ncoded + part]
-  Threads Ex;
-  if (ncoded) {
-    const char* xe = std::getenv("FSTAMD_STREAM_EXPANDERS");
-    const uint32_t T = (uint32_t)std::min(16, std::max(1, xe ? std::atoi(xe) : 4));
-    const uint8_t* const codes = (const uint8_t*)staging.p;
-    double* const w_out = out->weights + lbase;
+  // Phase 4.  Starts the expanders: thread t of T takes the t-th slice of every coded part,
+  // in part order.  It waits (host side) until the part's completion event has been recorded,
+  // then for the event itself, and only then reads the part's codes.  Nothing polls memory
+  // the device writes.
+  void start_expanders() {
+    recorded.reset(parts);
+    tx0 = std::chrono::steady_clock::now();
+    if (!ncoded) return;
+    const uint32_t T = knobs.expanders;
     x_ev.assign(T * ncoded, 0.0);
     x_end.assign(T * ncoded, 0.0);
-    for (uint32_t t = 0; t < T; ++t)
-      Ex.th.emplace_back([&, t, T, codes, w_out] {
-        if (hipSetDevice(dev) != hipSuccess) {
-          x_failed = true;
-          return;
-        }
-        for (size_t p = 0; p < ncoded; ++p) {
-          {
-            std::unique_lock<std::mutex> g(X.mu);
-            X.cv.wait(g, [&] { return X.abort || X.rec[p]; });
-            if (!X.rec[p]) return;
-          }
-          if (hipEventSynchronize(K->ev[parts + p]) != hipSuccess) {
-            x_failed = true;
-            return;
-          }
-          if (x_prof) x_ev[t * ncoded + p] = x_ms();
-          // (slices cut at 8 elements: whole lines of the weights for all but the ends)
-          const uint64_t a = loff[cut[p]], z = loff[cut[p + 1]], w = z - a;
-          const uint64_t lo = a + ((w * t / T) & ~7ull), hi = t + 1 == T ? z : a + ((w * (t + 1) / T) & ~7ull);
-          if (hi > lo) expand_weight_codes(codes + lo, hi - lo, code_table, w_out + lo);
-          if (x_prof) x_end[t * ncoded + p] = x_ms();
-        }
-      });
+    for (uint32_t t = 0; t < T; ++t) expanders.add([this, t, T] { expand(t, T); });
   }
-
-  // ---- the parts: engine A takes parts 0, 2, .., engine B 1, 3, .. (A all without B) ----
-  std::vector<FstError> perr(parts, FST_OK);
-  // (A/B timing only: FSTAMD_STREAM_AB=1 drops the copy-out; the result then lacks paths)
-  const char* abe = std::getenv("FSTAMD_STREAM_AB");
-  const bool ab_nocopy = abe && std::atoi(abe) == 1;
-  auto drive = [&](DeviceEngine::Lease& E, hipStream_t s, size_t p0, size_t step) {
+  void expand(uint32_t t, uint32_t T) {
+    const uint8_t* const codes = (const uint8_t*)staging.p;
+    double* const w_out = out->weights + lbase;
     if (hipSetDevice(dev) != hipSuccess) {
-      perr[p0] = FST_INVALID_ARG;
-      x_abort();
+      x_failed = true;
       return;
     }
-    for (size_t p = p0; p < parts; p += step) {
-      {
-        std::unique_lock<std::mutex> g(R.mu);
-        R.cv.wait(g, [&] { return R.failed || R.n > p; });
-        if (R.n <= p) {
-          perr[p] = FST_OOM;
-          x_abort();
-          return;
-        }
+    for (size_t p = 0; p < ncoded; ++p) {
+      if (!recorded.wait(p)) return;
+      if (hipEventSynchronize(K->ev[parts + p]) != hipSuccess) {
+        x_failed = true;
+        return;
       }
+      // (FSTAMD_HOST_PROF: when each part's event passed and when its expansion ended, ms
+      // from the expanders' start, per thread)
+      if (knobs.host_prof) x_ev[t * ncoded + p] = x_ms();
+      const auto [lo, hi] = expander_slice(loff[cut[p]], loff[cut[p + 1]], t, T);
+      if (hi > lo) expand_weight_codes(codes + lo, hi - lo, code_table, w_out + lo);
+      if (knobs.host_prof) x_end[t * ncoded + p] = x_ms();
+    }
+  }
+
+  // Phase 5.  Launches the parts: engine A takes parts 0, 2, .., engine B 1, 3, .. on a
+  // thread of its own (A all without B).  Errors land in perr.
+  void drive_parts() {
+    perr.assign(parts, FST_OK);
+    tk0 = std::chrono::steady_clock::now();
+    ThreadGroup second;
+    if (EB) second.add([this] { drive(EB, sB, 1, 2); });
+    drive(EA, sA, 0, EB ? 2 : 1);
+  }
+  void drive(DeviceEngine::Lease& E, hipStream_t s, size_t p0, size_t step) {
+    auto fail = [&](size_t p, FstError e) {
+      perr[p] = e;
+      recorded.abort();
+    };
+    if (hipSetDevice(dev) != hipSuccess) return fail(p0, FST_INVALID_ARG);
+    for (size_t p = p0; p < parts; p += step) {
+      if (!uploaded.wait_for(p)) return fail(p, FST_OOM);
       const uint32_t s0 = cut[p], np = cut[p + 1] - cut[p];
-      ChainInput in{(const uint32_t*)d_lab.p, (const uint64_t*)d_off.p + s0, np, max_len};
-      if (tm) in.text = (const uint8_t*)d_lab.p;  // (the bytes, in the labels' place)
+      ChainInput in{(const uint32_t*)d_lab->p, (const uint64_t*)d_off->p + s0, np, max_len};
+      if (tm) in.text = (const uint8_t*)d_lab->p;  // (the bytes, in the labels' place)
       BatchOutDev v = vb;
       v.status += s0;
       v.path_len += s0;
       v.path_off += s0;
       v.final_w += s0;
-      v.slots = (const uint64_t*)d_off.p + s0;
+      v.slots = (const uint64_t*)d_off->p + s0;
       const bool coded = p < ncoded;
       if (tm) {
         v.text = (const TextOutDev*)d_tx->p + p;
@@ -441,96 +417,94 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
         v.host_w = out->weights + lbase;
       }
       // (label mode only: without its emission the text route has no result at all)
-      if (ab_nocopy && !tm && !coded) v.host_ol = nullptr, v.host_w = nullptr;
-      v.first_status = (int32_t*)d_first.p + s0;
+      if (knobs.ab_nocopy && !tm && !coded) v.host_ol = nullptr, v.host_w = nullptr;
+      v.first_status = (int32_t*)d_first->p + s0;
       // the pull tier alone: no fill, copy or host synchronisation between parts (a fill
       // or copy is a blit kernel that waits for CU slots behind the other engine's
       // persistent kernel, and had held this engine's next part back); the later tiers
       // and the downloads come after the last part
       if (hipStreamWaitEvent(s, K->ev[p], 0) != hipSuccess ||
-          E->launch_pull_part(D, in, n, semantics, v, s, (unsigned int*)d_ctr.p + p, tm, coded) !=
+          E->launch_pull_part(D, in, n, semantics, v, s, (unsigned int*)d_ctr->p + p, tm, coded) !=
               hipSuccess ||
-          (coded && hipEventRecord(K->ev[parts + p], s) != hipSuccess)) {
-        perr[p] = FST_OOM;
-        x_abort();
-        return;
-      }
-      if (coded) {  // the part's completion event is in the stream: its expanders may wait
-        std::lock_guard<std::mutex> g(X.mu);
-        X.rec[p] = 1;
-        X.cv.notify_all();
-      }
+          (coded && hipEventRecord(K->ev[parts + p], s) != hipSuccess))
+        return fail(p, FST_OOM);
+      // the part's completion event is in the stream: its expanders may wait
+      if (coded) recorded.mark(p);
     }
-  };
-  const auto tk0 = std::chrono::steady_clock::now();
-  {
-    Threads P;
-    if (EB) P.th.emplace_back([&] { drive(EB, sB, 1, 2); });
-    drive(EA, sA, 0, EB ? 2 : 1);
-    P.join();
   }
-  for (hipStream_t x : {up, sA, sB})
-    if (x && hipStreamSynchronize(x) != hipSuccess) return FST_OOM;
-  for (size_t p = 0; p < parts; ++p)
-    if (perr[p] != FST_OK) return perr[p];
-  int32_t* const st_out = (tm ? io.tout->status : out->status) + S.s0;
-  // (text mode: the total weights in the final weights' place, and the byte counts)
-  double* const fin_out = (tm ? io.tout->total_weight : out->final_weights) + S.s0;
-  const void* const d_fin = tm ? d_tw->p : o.fin.p;
-  int32_t* const first = first_all + S.s0;
-  // statuses, final weights and the pull tier's statuses in one download each
-  auto download = [&](bool with_first) {
-    return d2h(st_out, o.status.p, num * 4ull, sA) && d2h(fin_out, d_fin, num * 8ull, sA) &&
+
+  // Statuses, final weights (text mode: total weights and byte counts) and, with_first, the
+  // pull tier's statuses, in one download each on sA, waited for.
+  bool download(bool with_first) {
+    return d2h(st_out, o->status.p, num * 4ull, sA) &&
+           d2h(fin_out, tm ? d_tw->p : o->fin.p, num * 8ull, sA) &&
            (!tm || d2h(io.nbytes + S.s0, d_nb->p, num * 4ull, sA)) &&
-           (!with_first || d2h(first, d_first.p, num * 4ull, sA)) &&
+           (!with_first || d2h(first, d_first->p, num * 4ull, sA)) &&
            hipStreamSynchronize(sA) == hipSuccess;
-  };
-  // (an error return here leaves expanders in flight: they are joined on the way out)
-  if (!download(true) || fault_inject("stream_after_pull")) return FST_OOM;
-  // the expanders, before anything else writes the result's weights: what the later tiers
-  // finish is downloaded over whatever the expanders made of those strings' unwritten codes
-  Ex.join();
-  if (x_failed) return FST_OOM;
-  if (x_prof && ncoded) {
-    const size_t T = x_ev.size() / ncoded;
-    for (size_t p = 0; p < ncoded; ++p) {
-      double e0 = x_ev[p], e1 = 0;
-      for (size_t t = 0; t < T; ++t) {
-        e0 = std::min(e0, x_ev[t * ncoded + p]);
-        e1 = std::max(e1, x_end[t * ncoded + p]);
+  }
+
+  // Phase 6.  Waits for the uploads and the parts, reports a part's error, brings the
+  // statuses down.  (An error return here may leave expanders in flight.)
+  FstError sync_and_download() {
+    for (hipStream_t x : {up, sA, sB})
+      if (x && hipStreamSynchronize(x) != hipSuccess) return FST_OOM;
+    for (size_t p = 0; p < parts; ++p)
+      if (perr[p] != FST_OK) return perr[p];
+    if (!download(true) || fault_inject("stream_after_pull")) return FST_OOM;
+    return FST_OK;
+  }
+
+  // Phase 7.  Joins the expanders, before anything else writes the result's weights: what the
+  // later tiers finish is downloaded over whatever the expanders made of those strings'
+  // unwritten codes.
+  FstError join_expanders() {
+    expanders.join();
+    if (x_failed) return FST_OOM;
+    if (knobs.host_prof && ncoded) {
+      const size_t T = x_ev.size() / ncoded;
+      for (size_t p = 0; p < ncoded; ++p) {
+        double e0 = x_ev[p], e1 = 0;
+        for (size_t t = 0; t < T; ++t) {
+          e0 = std::min(e0, x_ev[t * ncoded + p]);
+          e1 = std::max(e1, x_end[t * ncoded + p]);
+        }
+        std::fprintf(stderr, "[libfst_amd stream] part %zu labels %llu event +%.3f ms expanded +%.3f ms\n",
+                     p, (unsigned long long)(loff[cut[p + 1]] - loff[cut[p]]), e0, e1);
       }
-      std::fprintf(stderr, "[libfst_amd stream] part %zu labels %llu event +%.3f ms expanded +%.3f ms\n",
-                   p, (unsigned long long)(loff[cut[p + 1]] - loff[cut[p]]), e0, e1);
+      std::fprintf(stderr, "[libfst_amd stream] expanders joined +%.3f ms\n", x_ms());
     }
-    std::fprintf(stderr, "[libfst_amd stream] expanders joined +%.3f ms\n", x_ms());
+    return FST_OK;
   }
-  // the later tiers, once, over the strings the pull tier handed on (in the device arena,
-  // the same slots) -- only when it handed some on (the metric: none), then the statuses
-  // and final weights again
-  bool handed = false;
-  for (uint32_t i = 0; i < num && !handed; ++i) handed = first[i] != kPathOk && first[i] != kPathEmpty;
-  uint32_t launches = (uint32_t)parts;
-  if (tm && std::getenv("FSTAMD_SHARD_LOG")) {  // tests (text mode): what the pull tier handed on
-    uint32_t nh = 0;
-    for (uint32_t i = 0; i < num; ++i) nh += first[i] != kPathOk && first[i] != kPathEmpty;
-    std::fprintf(stderr, "[libfst_amd stream] dev %d strings %u..%u parts %zu handed-on %u\n", dev,
-                 S.s0, S.s1, parts, nh);
-  }
-  if (handed) {
+
+  // Phase 8.  The later tiers, once, over the strings the pull tier handed on (in the device
+  // arena, the same slots) -- only when it handed some on (the metric: none), then the
+  // statuses and final weights again.  Takes later_mu and keeps it to the end of the run.
+  FstError later_tiers() {
+    auto handed_on = [&](uint32_t i) { return first[i] != kPathOk && first[i] != kPathEmpty; };
+    bool handed = false;
+    for (uint32_t i = 0; i < num && !handed; ++i) handed = handed_on(i);
+    launches = (uint32_t)parts;
+    if (tm && knobs.shard_log) {  // tests (text mode): what the pull tier handed on
+      uint32_t nh = 0;
+      for (uint32_t i = 0; i < num; ++i) nh += handed_on(i);
+      std::fprintf(stderr, "[libfst_amd stream] dev %d strings %u..%u parts %zu handed-on %u\n", dev,
+                   S.s0, S.s1, parts, nh);
+    }
+    if (!handed) return FST_OK;
     later_lock.lock();
-    ChainInput in{(const uint32_t*)d_lab.p, (const uint64_t*)d_off.p, num, max_len};
+    ChainInput in{(const uint32_t*)d_lab->p, (const uint64_t*)d_off->p, num, max_len};
     // text mode: the later tiers read 4-B labels -- the shard's bytes widened once, now
     // (only batches that hand strings on pay for the buffer and the kernel)
     if (tm) {
       d_lab4 = std::make_unique<DevBuf>(std::max<uint64_t>(total, 1) * 4);
       if (!d_lab4->p ||
-          EA->widen_text((const uint8_t*)d_lab.p, (const uint64_t*)d_off.p, num,
+          EA->widen_text((const uint8_t*)d_lab->p, (const uint64_t*)d_off->p, num,
                          (uint32_t*)d_lab4->p, sA) != hipSuccess)
         return FST_OOM;
       in.labels = (const uint32_t*)d_lab4->p;
     }
     BatchOutDev v = vb;
-    v.slots = (const uint64_t*)d_off.p;
+    v.slots = (const uint64_t*)d_off->p;
     EA->set_after_pull(true);
     hipError_t e = EA->run_chain(D, in, n, semantics, v, sA, nullptr);
     EA->set_after_pull(false);
@@ -539,22 +513,25 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
     if (tm && e == hipSuccess)
       e = EA->text_fixup(v, TextOutDev{io.tout->text + lbase, (uint32_t*)d_nb->p,
                                        (double*)d_tw->p},
-                         (const int32_t*)d_first.p, num, sA);
+                         (const int32_t*)d_first->p, num, sA);
     if (e != hipSuccess || !download(false)) return FST_OOM;
     ++launches;
+    return FST_OK;
   }
 
-  // ---- paths the later tiers wrote (device arena, same slots) ----
-  uint64_t nfix = 0;
-  if (!tm)
-    for (uint32_t i = 0; i < num; ++i) nfix += st_out[i] == kPathOk && first[i] != kPathOk;
-  if (nfix) {
+  // Phase 9.  Brings down the paths the later tiers wrote (device arena, same slots): one by
+  // one when few, else the whole arena.
+  FstError download_fixups() {
+    auto fixed = [&](uint32_t i) { return st_out[i] == kPathOk && first[i] != kPathOk; };
+    uint64_t nfix = 0;
+    if (!tm)
+      for (uint32_t i = 0; i < num; ++i) nfix += fixed(i);
+    if (!nfix) return FST_OK;
     bool ok = true;
-    const char* few_env = std::getenv("FSTAMD_STREAM_FIX_FEW");  // (tests: 0 = bulk copy)
-    const uint64_t few = few_env ? std::strtoull(few_env, nullptr, 10) : 4096ull;
+    const uint64_t few = knobs.fix_few;  // (tests: 0 = bulk copy)
     if (nfix <= few) {
       for (uint32_t i = 0; i < num && ok; ++i)
-        if (st_out[i] == kPathOk && first[i] != kPathOk) {
+        if (fixed(i)) {
           const uint64_t a = loff[i], L = loff[i + 1] - a;
           ok = d2h(out->olabels + lbase + a, vb.out_ol + a, L * 4, sA) &&
                d2h(out->weights + lbase + a, vb.out_w + a, L * 8, sA);
@@ -573,12 +550,42 @@ FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const ui
           expand_weight_codes((const uint8_t*)staging.p + a, L, code_table,
                               out->weights + lbase + a);
         }
+    return FST_OK;
   }
-  Th.join();
-  S.launches = launches;
-  S.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk0)
-                  .count();
-  return FST_OK;
+
+  // Phase 10.  Joins the uploader and the copiers: the result's ilabels are complete.
+  void finish() {
+    uploads.join();
+    S.launches = launches;
+    S.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk0)
+                    .count();
+  }
+};
+
+FstError stream_shard(StreamShard& S, DeviceFst& D, const StreamIo& io, const StreamKnobs& knobs,
+                      const uint64_t* poff, uint32_t max_len, uint32_t n, int semantics,
+                      int32_t* first_all, std::mutex* later_mu) {
+  if (hipSetDevice(S.dev) != hipSuccess) return FST_INVALID_ARG;
+  if (S.s1 == S.s0) return FST_OK;
+  ShardRun R(S, D, io, knobs, poff, max_len, n, semantics, first_all, later_mu);
+  FstError e = R.plan();
+  if (e == FST_OK) e = R.acquire();
+  if (e != FST_OK) return e;
+  R.start_uploads();
+  R.start_expanders();
+  R.drive_parts();
+  e = R.sync_and_download();
+  if (e == FST_OK) e = R.join_expanders();
+  if (e == FST_OK) e = R.later_tiers();
+  if (e == FST_OK) e = R.download_fixups();
+  if (e == FST_OK) R.finish();
+  return e;
+}
+
+// every array of a result came pinned from the pool (or the caller takes another route)
+template <class... P>
+bool all_pinned(const P*... p) {
+  return (pin_is_pinned(p) && ...);
 }
 
 }  // namespace
@@ -622,6 +629,7 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b, St
                  const uint64_t* offsets, uint32_t num, uint32_t n, int semantics) {
   const bool tm = io.text_mode();
   FstBatchResult* const out = io.out;  // (label mode)
+  const StreamKnobs knobs = StreamKnobs::from_env();
   DeviceRestore_ restore;
   std::vector<DeviceFst*> Ds(devices.size(), nullptr);
   for (size_t d = 0; d < devices.size(); ++d) {  // (the rhs goes to every device first)
@@ -634,7 +642,7 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b, St
   // before the result exists: a call with more parts than the route takes, or whose stream
   // kit or events cannot be created, goes the pipelined way instead of failing
   {
-    const size_t max_parts = std::max(stream_cuts(false).size(), stream_cuts(true).size()) + 1;
+    const size_t max_parts = std::max(knobs.cuts(false).size(), knobs.cuts(true).size()) + 1;
     if (max_parts > kStreamMaxParts) return kStreamNotApplicable;
     for (int dev : devices) {
       KitLease K(dev);
@@ -645,16 +653,14 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b, St
   if (tm) {
     FstTextResult* const t = io.tout;
     if (!alloc_text_result(t, num, total)) return FST_OOM;
-    if (!pin_is_pinned(t->status) || !pin_is_pinned(t->text_offsets) ||
-        !pin_is_pinned(t->total_weight) || !pin_is_pinned(t->text)) {
+    if (!all_pinned(t->status, t->text_offsets, t->total_weight, t->text)) {
       fst_text_result_free(t);
       return kStreamNotApplicable;
     }
   } else {
     if (!alloc_result(out, num, total)) return FST_OOM;
-    if (!pin_is_pinned(out->ilabels) || !pin_is_pinned(out->olabels) ||
-        !pin_is_pinned(out->weights) || !pin_is_pinned(out->path_offsets) ||
-        !pin_is_pinned(out->status) || !pin_is_pinned(out->final_weights)) {
+    if (!all_pinned(out->ilabels, out->olabels, out->weights, out->path_offsets, out->status,
+                    out->final_weights)) {
       fst_batch_result_free(out);
       return kStreamNotApplicable;
     }
@@ -690,7 +696,7 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b, St
   // ---- shards: contiguous string ranges of equal estimated cost ----
   nsh = std::max<uint32_t>(1, std::min<uint32_t>(nsh, num));
   std::vector<StreamShard> sh(nsh);
-  const bool shard_log = std::getenv("FSTAMD_SHARD_LOG") != nullptr;
+  const bool shard_log = knobs.shard_log;
   std::vector<double> pre;  // cost of strings [0, i) (chain_cost per distinct length)
   if (nsh > 1 || shard_log) {
     std::vector<double> cl(max_len + 1, -1.0);
@@ -702,17 +708,7 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b, St
     }
   }
   {
-    std::vector<uint32_t> cuts{0};
-    if (nsh > 1) {
-      for (uint32_t j = 1; j < nsh; ++j) {
-        const double goal = pre[num] * j / nsh;
-        uint32_t i = (uint32_t)(std::lower_bound(pre.begin(), pre.end(), goal) - pre.begin());
-        i = std::max(i, cuts.back() + 1);          // never empty
-        i = std::min(i, num - (nsh - j));           // at least one string for each later one
-        cuts.push_back(i);
-      }
-    }
-    cuts.push_back(num);
+    const std::vector<uint32_t> cuts = stream_shard_cuts(pre, num, nsh);
     for (uint32_t j = 0; j < nsh; ++j) {
       sh[j].dev = devices[j % devices.size()];
       sh[j].s0 = cuts[j];
@@ -726,14 +722,14 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b, St
                    tm ? "streamed-text" : "streamed");
 
   PinnedVec<int32_t> first(std::max<uint32_t>(num, 1));
-  std::vector<std::mutex> later_mu(devices.size());  // (stream_shard: per device)
+  std::vector<std::mutex> later_mu(devices.size());  // (ShardRun::later_tiers: per device)
   if (t_prof) t_prof->lap(0);
   const auto tk0 = std::chrono::steady_clock::now();
   {
     auto run = [&](uint32_t j) {
       StreamShard& S = sh[j];
       const size_t d = (size_t)(j % devices.size());
-      S.err = stream_shard(S, *Ds[d], io, poff, max_len, n, semantics, first.data(),
+      S.err = stream_shard(S, *Ds[d], io, knobs, poff, max_len, n, semantics, first.data(),
                            &later_mu[d]);
     };
     std::vector<std::thread> th;
@@ -756,24 +752,8 @@ int run_streamed(const std::vector<int>& devices, uint32_t nsh, FrozenFst& b, St
     FstTextResult* const t = io.tout;
     t->total_bytes = text_compact(num, poff, io.nbytes, t->status, t->total_weight, t->text);
   } else {  // ---- strings without a path: their slots dropped (in order, moving left) ----
-    uint64_t nbad = 0;
-    for (uint32_t i = 0; i < num; ++i) nbad += out->status[i] != kPathOk;
-    if (nbad) {
-      uint64_t dst = 0;
-      for (uint32_t i = 0; i < num; ++i) {
-        const uint64_t a = poff[i], L = poff[i + 1] - a;
-        poff[i] = dst;
-        if (out->status[i] != kPathOk) continue;
-        if (dst != a) {
-          std::memmove(out->ilabels + dst, out->ilabels + a, L * 4);
-          std::memmove(out->olabels + dst, out->olabels + a, L * 4);
-          std::memmove(out->weights + dst, out->weights + a, L * 8);
-        }
-        dst += L;
-      }
-      poff[num] = dst;
-    }
-    out->total_arcs = poff[num];
+    out->total_arcs =
+        paths_compact(num, poff, out->status, out->ilabels, out->olabels, out->weights);
   }
   if (t_prof) {
     t_prof->runs = (int)agg.launches;

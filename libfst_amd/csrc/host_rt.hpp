@@ -2,6 +2,10 @@
 // pooled buffers, the per-call profile, the shard types and the batch routes' signatures.
 // c_api.cpp holds the handle tables and the single calls, host_rt.cpp the pools and small
 // helpers, batch_sharded.cpp / batch_streamed.cpp the routes, batch_entries.cpp fst_batch.h.
+// stream_plan.hpp (included here, no HIP in it) holds what those routes decide and hand over on
+// the host alone: the streamed batch's knobs (StreamKnobs), its part and shard cuts, the label
+// route's compaction, and the gates and thread groups (PartGate, RecordedGate, ThreadGroup)
+// of run_pipelined's uploader and of batch_streamed.cpp's ShardRun.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +24,7 @@
 #include "../../include/fst_batch.h"
 #include "device_engine.hpp"
 #include "host_fst.hpp"
+#include "stream_plan.hpp"
 
 #pragma GCC visibility push(hidden)  // internal: nothing here joins the library's exports
 namespace fstamd::host {

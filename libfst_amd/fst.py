@@ -192,6 +192,7 @@ SIGNATURES = {
     "fst_debug_text_compact": (_u64, [_u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     "fst_debug_expand_weight_codes": (None, [C.c_void_p, _u64, C.c_void_p, C.c_void_p]),
+    "fst_debug_stream_part_cuts": (_u32, [C.c_void_p, _u32, C.c_void_p, _u32, C.c_void_p]),
 }
 
 _lib = None
@@ -805,6 +806,18 @@ def debug_expand_weight_codes(codes, table, dst):
     assert dst.shape == codes.shape and dst.flags.writeable
     lib().fst_debug_expand_weight_codes(codes.ctypes.data, codes.size, table.ctypes.data,
                                         dst.ctypes.data)
+
+
+def debug_stream_part_cuts(offsets, per_mille):
+    """The streamed batch's part planner (fst_debug_stream_part_cuts): the string boundaries
+    [0, .., num] of the parts of a shard with these label offsets, cut at these per-mille
+    fractions of its labels.  Runs without a GPU."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    per_mille = np.ascontiguousarray(per_mille, dtype=np.uint64)
+    cuts = np.zeros(per_mille.size + 2, dtype=np.uint32)
+    n = lib().fst_debug_stream_part_cuts(offsets.ctypes.data, offsets.size - 1,
+                                         per_mille.ctypes.data, per_mille.size, cuts.ctypes.data)
+    return cuts[:n]
 
 
 def coalescer_state(device: int = 0):
