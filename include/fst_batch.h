@@ -280,6 +280,19 @@ typedef struct {
 } FstLatticeBatch;
 
 #define FST_LATTICE_PROJECT_OUTPUT 1u   /* every arc's ilabel := its olabel (project.zig, .output) */
+/* Item i is connect(fst_compose_frozen(a_i, b)) (src/ops/connect.zig:17-124), bit for bit: the
+ * states that can reach a final state are kept (compose output is accessible by construction)
+ * and renumbered in increasing old id, a kept state's arcs are its old arcs whose target is
+ * kept, in their order, with labels and weights copied bit for bit; a final weight of -inf
+ * comes out +inf (isFinal is !isInf).  An OK item whose start cannot reach a final state is the
+ * reference's empty FST: zero states, start = FST_NO_STATE.  Non-OK items are as without the
+ * flag; with FST_LATTICE_PROJECT_OUTPUT as well the only difference remains ilabels[k] =
+ * olabels[k].  fst_device_compose_frozen reports the trimmed totals in `needed`.  The trim runs
+ * on the device before the compaction, so what shrinks is the compacted result, its download
+ * and everything downstream; peak device memory does not.  Opt-in: on lattices without dead
+ * ends the pass costs time and removes nothing.
+ * The value is 4, not 2: bit 1 is not assigned and stays an unknown flag (FST_INVALID_ARG). */
+#define FST_LATTICE_CONNECT 4u
 
 FstError fst_compose_frozen_batch(FstHandle b, const uint32_t* labels, const uint64_t* offsets,
                                   uint32_t num_strings, uint32_t lattice_flags,
@@ -287,6 +300,25 @@ FstError fst_compose_frozen_batch(FstHandle b, const uint32_t* labels, const uin
 FstError fst_compose_frozen_lhs_batch(FstHandle b, const FstLhsBatch* lhs, uint32_t lattice_flags,
                                       const FstBatchOptions* opts, FstLatticeBatch* out);
 void fst_lattice_batch_free(FstLatticeBatch* r);
+
+/* Connect (trim) of every item of an lhs batch, with no compose: a recogniser's lattices before
+ * they meet a grammar, or a lattice batch the caller has rescored.  Item i of the result is
+ * connect(lhs_i) as src/ops/connect.zig:17-124 returns it, bit for bit: kept = reachable from
+ * the start and able to reach a final state (final: the weight is not +-inf, so NaN is final);
+ * new id = rank among the kept states in increasing old id; a kept state's final weight is
+ * copied when final and +inf otherwise; its arcs are the old arcs whose target is kept, in the
+ * old order.  The result's start is the renumbered old start (it need not be 0).  No start, no
+ * states or a start that is not kept: zero states, start = FST_NO_STATE.
+ * Every item is FST_PATH_OK: connect never compares weights, so NaN weights are copied, not
+ * refused -- unlike the compose entries, which report FST_PATH_UNSUPPORTED for them.
+ * The same validator as the other lhs entries runs first (a failed check: FST_INVALID_ARG with
+ * *out zeroed; also a null lhs / out, unknown opts->flags).  num_fsts == 0 gives the empty OK
+ * result.  There is no rhs and opts->semantics is ignored.  FST_BATCH_DEVICES shards by arcs + 1
+ * per item; a sharded result is byte-identical to a one-shard run.  fst_last_launch_stats
+ * reports engine 11 (the compose entries keep 10 and count the trim kernels in `launches`).
+ * Free with fst_lattice_batch_free. */
+FstError fst_connect_lhs_batch(const FstLhsBatch* lhs, const FstBatchOptions* opts,
+                               FstLatticeBatch* out);
 
 /* The device-resident form, chains in and lattices out, so that a cascade never leaves the
  * device.  Every pointer in `out` is device memory on opts->device, in FstLhsBatch's layout: a
@@ -410,7 +442,9 @@ typedef struct {
                                    7 = lazy pull tier,
                                    8 = lhs batch, lazy (hashed replay, one wave per lhs),
                                    9 = lhs batch, eager (general BFS tiers, 1-best in kernel),
-                                   10 = lattice batch (general BFS tiers, lattice emission) */
+                                   10 = lattice batch (general BFS tiers, lattice emission;
+                                        with FST_LATTICE_CONNECT the trim kernels too),
+                                   11 = fst_connect_lhs_batch (the lattice trim alone) */
     uint32_t grid;              /* workgroups of the dominant kernel */
 } FstLaunchStats;
 FstError fst_last_launch_stats(FstLaunchStats* out);

@@ -166,7 +166,9 @@ FstError empty_result(FstLatticeBatch* out) {
   const_cast<uint64_t*>(out->fsts.arc_offsets)[0] = 0;
   return FST_OK;
 }
-bool lattice_flags_ok(uint32_t f) { return !(f & ~FST_LATTICE_PROJECT_OUTPUT); }
+bool lattice_flags_ok(uint32_t f) {
+  return !(f & ~(FST_LATTICE_PROJECT_OUTPUT | FST_LATTICE_CONNECT));  // (bit 1 stays unknown)
+}
 
 // A checked batch of general lhs through `fs` (one stage: the lhs batch entry; several: stage
 // 1 on the lhs, then chain stages on the 1-best output tapes) into a label or a text result.
@@ -395,6 +397,27 @@ FstError fst_compose_frozen_lhs_batch(FstHandle b_handle, const FstLhsBatch* lhs
   return call.close(e, "fst_compose_frozen_lhs_batch", out, fst_lattice_batch_free);
 }
 
+// Connect of every item of an lhs batch: no rhs, no engine ladder; the items are staged as the
+// lhs entries stage them and trimmed in place of a compose (run_connect_shard).
+FstError fst_connect_lhs_batch(const FstLhsBatch* lhs, const FstBatchOptions* opts,
+                               FstLatticeBatch* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!lhs_batch_valid(lhs) || !flags_ok(opts)) return FST_INVALID_ARG;
+  const uint32_t num = lhs->num_fsts;
+  if (num == 0) return empty_result(out);
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  std::vector<double> cost(call.nsh > 1 ? num : 0);
+  for (size_t i = 0; i < cost.size(); ++i)
+    cost[i] = (double)(lhs->arc_offsets[lhs->state_offsets[i + 1]] -
+                       lhs->arc_offsets[lhs->state_offsets[i]]) + 1.0;
+  const FstError e = run_sharded(
+      call.devices, call.nsh, num, cost, [&](Shard& S) { return run_connect_shard(S, *lhs); },
+      out);
+  return call.close(e, "fst_connect_lhs_batch", out, fst_lattice_batch_free);
+}
+
 void fst_lattice_batch_free(FstLatticeBatch* r) {
   if (!r) return;
   pin_release(r->status);
@@ -469,7 +492,9 @@ FstError fst_device_compose_frozen(FstHandle b_handle, const uint32_t* d_labels,
   if (needed[0] > lat->arena.state_cap || needed[1] > lat->arena.arc_cap) return FST_OOM;
   // too small: the statuses and `needed` stand, nothing else is written
   if (needed[0] > csr.state_cap || needed[1] > csr.arc_cap) return FST_OK;
-  if (E->compact_lattices(lat->arena, num_strings, csr, s) != hipSuccess) return FST_OOM;
+  if (E->compact_lattices(lat->arena, num_strings, csr, s, lat->connect ? &lat->trim : nullptr) !=
+      hipSuccess)
+    return FST_OOM;
   return FST_OK;  // (the drain waits for the gather, then `keep` and `lat` go)
 }
 

@@ -208,10 +208,15 @@ FstError shard_lattice_compact(Shard& S) {
   csr.state_cap = needed[0];
   csr.arc_cap = needed[1];
   // (synchronised: the download may run on another engine's stream)
-  if (S.E->compact_lattices(Ls.arena, num, csr, stream) != hipSuccess ||
+  if (S.E->compact_lattices(Ls.arena, num, csr, stream, Ls.connect ? &Ls.trim : nullptr) !=
+          hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess)
     return FST_OOM;
   drain.done = true;
+  for (auto* b : {&Ls.tmark, &Ls.tqueue, &Ls.troff, &Ls.trcur, &Ls.trsrc, &Ls.tlist, &Ls.tctr,
+                  &Ls.tstart})
+    b->reset();
+  Ls.input.reset();
   Ls.item.reset();
   Ls.afin.reset();
   Ls.aaoff.reset();
@@ -740,8 +745,8 @@ FstError stage_lhs_items(Shard& S, DeviceFst* D, const FstLhsBatch& L, hipStream
     d.start = d.num_states ? L.start[i0 + i] : kNoState;
     d.num_arcs = (uint32_t)(a1 - a0);
     uint32_t fl = 0;
-    if (D->nan) fl |= kLhsNaN;
-    if (!D->nonneg) fl |= kLhsReplay;
+    if (D && D->nan) fl |= kLhsNaN;  // (no rhs: fst_connect_lhs_batch, which reads no flag)
+    if (D && !D->nonneg) fl |= kLhsReplay;
     uint32_t* so = soff + (s0 - sb) + i;
     for (uint64_t s = s0; s <= s1; ++s) so[s - s0] = (uint32_t)(L.arc_offsets[s] - a0);
     for (uint64_t s = s0; s < s1; ++s) {
@@ -832,6 +837,144 @@ bool alloc_lattice_result(FstLatticeBatch* out, uint32_t num, uint64_t states, u
          F.ilabels && F.olabels && F.nextstates && F.weights;
 }
 
+// ---- Lattice trim (connect) ---------------------------------------------------------------
+
+FstError trim_lattices(DeviceEngine::Lease& E, const int32_t* status, LatShard& L, uint32_t num,
+                       hipStream_t stream) {
+  if (num == 0) return FST_OK;
+  const LatticeOutDev& a = L.arena;
+  const bool access = L.tstart != nullptr;
+  uint32_t sweeps = 4;  // a compose lattice settles in one or two; tests: FSTAMD_TRIM_SWEEPS
+  if (const char* e = std::getenv("FSTAMD_TRIM_SWEEPS"))
+    if (*e) sweeps = (uint32_t)std::min<unsigned long long>(std::strtoull(e, nullptr, 10), 1u << 20);
+  uint32_t cap = 0xFFFFFFFFu;
+  if (const char* g = std::getenv("FSTAMD_GRAPH_GRID"))
+    if (std::atoi(g) > 0) cap = (uint32_t)std::atoi(g);
+  const uint32_t cus = (uint32_t)std::max(E->num_cus(), 1);
+  const uint32_t grid_wave = std::max<uint32_t>(1, std::min({num, cus * 32, cap}));
+  const uint32_t grid_wg = std::max<uint32_t>(1, std::min({num, cus * 8, cap}));
+  const uint64_t sb = (a.state_cap + 4) * 4, ab = (a.arc_cap + 4) * 4;
+  L.tmark = std::make_unique<DevBuf>(sb);
+  L.tlist = std::make_unique<DevBuf>(num * 4ull);
+  L.tctr = std::make_unique<DevBuf>(64);
+  if (access) L.tqueue = std::make_unique<DevBuf>(sb);
+  if (!L.tmark->p || !L.tlist->p || !L.tctr->p || (access && !L.tqueue->p)) return FST_OOM;
+  // every return drains the stream before the workspace (and the caller's arena) can go
+  StreamDrain drain{{stream}};
+  LatTrimDev& t = L.trim;
+  t.mark = (uint32_t*)L.tmark->p;
+  t.queue = access ? (uint32_t*)L.tqueue->p : nullptr;
+  t.roff = t.rcur = t.rsrc = nullptr;
+  t.list = (uint32_t*)L.tlist->p;
+  t.tot = (unsigned long long*)L.tctr->p;
+  t.ctr = (uint32_t*)((uint8_t*)L.tctr->p + 32);
+  t.start = access ? (const uint32_t*)L.tstart->p : nullptr;
+  t.sweeps = sweeps;
+  t.access = access ? 1u : 0u;
+  struct Events {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  if (hipEventCreate(&ev.e[0]) != hipSuccess || hipEventCreate(&ev.e[1]) != hipSuccess)
+    return FST_OOM;
+  uint32_t launches = 0;
+  if (hipMemsetAsync(L.tctr->p, 0, 64, stream) != hipSuccess ||
+      hipEventRecord(ev.e[0], stream) != hipSuccess)
+    return FST_OOM;
+  if (access) {
+    if (launch_trim_access(a, t, status, num, grid_wg, stream) != hipSuccess) return FST_OOM;
+    ++launches;
+  }
+  if (launch_trim_sweep(a, t, status, num, grid_wave, stream) != hipSuccess) return FST_OOM;
+  ++launches;
+  PinnedVec<uint32_t> back(16);  // tot[4] as 8 words, then ctr
+  if (!d2h(back.data(), L.tctr->p, 64, stream) || hipStreamSynchronize(stream) != hipSuccess)
+    return FST_OOM;
+  const uint32_t handed = back[8 + kTrimCtrList];
+  if (handed > num) return FST_OOM;  // (a bug: the list holds an item at most once)
+  if (handed) {
+    L.troff = std::make_unique<DevBuf>(sb);
+    L.trcur = std::make_unique<DevBuf>(sb);
+    L.trsrc = std::make_unique<DevBuf>(ab);
+    if (!L.tqueue) L.tqueue = std::make_unique<DevBuf>(sb);
+    if (!L.troff->p || !L.trcur->p || !L.trsrc->p || !L.tqueue->p) return FST_OOM;
+    t.roff = (uint32_t*)L.troff->p;
+    t.rcur = (uint32_t*)L.trcur->p;
+    t.rsrc = (uint32_t*)L.trsrc->p;
+    t.queue = (uint32_t*)L.tqueue->p;
+    if (launch_trim_linear(a, t, status, std::max<uint32_t>(1, std::min({handed, cus * 8, cap})),
+                           stream) != hipSuccess)
+      return FST_OOM;
+    ++launches;
+  }
+  if (launch_trim_finalize(a, t, status, num, grid_wave, stream) != hipSuccess) return FST_OOM;
+  ++launches;
+  if (hipEventRecord(ev.e[1], stream) != hipSuccess ||
+      !d2h(back.data(), L.tctr->p, 64, stream) || hipStreamSynchronize(stream) != hipSuccess)
+    return FST_OOM;
+  drain.done = true;
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) != hipSuccess) ms = 0.f;
+  t_last_stats.kernel_ms += ms;
+  t_last_stats.launches += launches;
+  if (std::getenv("FSTAMD_ROUTE_LOG")) {
+    unsigned long long tot[4];
+    std::memcpy(tot, back.data(), sizeof(tot));
+    std::fprintf(stderr,
+                 "[libfst_amd route] lattice trim: items %u | sweep %u linear %u | states %llu -> "
+                 "%llu arcs %llu -> %llu | %.3f ms\n",
+                 back[8 + kTrimCtrSweep] + back[8 + kTrimCtrLinear], back[8 + kTrimCtrSweep],
+                 back[8 + kTrimCtrLinear], tot[0], tot[1], tot[2], tot[3], ms);
+  }
+  return FST_OK;
+}
+
+FstError run_connect_shard(Shard& S, const FstLhsBatch& L) {
+  const int dev = S.E->dev();
+  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  const hipStream_t stream = S.E.stream();
+  const uint32_t num = S.s1 - S.s0;
+  auto st = std::make_shared<LhsStaged>();
+  auto Lt = std::make_unique<LatShard>();
+  auto out = std::make_unique<DevOut>(num, 1);  // the statuses: every item is OK
+  // every return drains the stream before the staged blocks and the arena's buffers go
+  StreamDrain drain{{stream}};
+  if (FstError e = stage_lhs_items(S, nullptr, L, stream, st.get()); e != FST_OK) return e;
+  Lt->item = std::make_unique<DevBuf>(num * sizeof(LatItem));
+  Lt->tstart = std::make_unique<DevBuf>(num * 4ull);
+  if (!out->ok() || !Lt->item->p || !Lt->tstart->p) return FST_OOM;
+  // the arena is the staged batch itself, read in place (item i's arc offsets sit i words on)
+  LatticeOutDev& a = Lt->arena;
+  a.item = (LatItem*)Lt->item->p;
+  a.fin = const_cast<double*>(st->g.final_w);
+  a.aoff = const_cast<uint32_t*>(st->g.state_off);
+  a.il = const_cast<uint32_t*>(st->g.arc_il);
+  a.ol = const_cast<uint32_t*>(st->g.arc_ol);
+  a.w = const_cast<double*>(st->g.arc_w);
+  a.next = const_cast<uint32_t*>(st->g.arc_next);
+  a.state_cap = st->num_states;
+  a.arc_cap = st->num_arcs;
+  Lt->connect = true;
+  Lt->trim.aoff_skew = 1;
+  if (launch_trim_stage(st->in.lhs_desc, num, a.item, out->v.status, (uint32_t*)Lt->tstart->p,
+                        stream) != hipSuccess)
+    return FST_OOM;
+  LaunchStats ls;
+  ls.engine = 11;
+  ls.launches = 1;
+  ls.grid = std::max<uint32_t>(1, std::min<uint32_t>(num, (uint32_t)S.E->num_cus() * 32));
+  t_last_stats = ls;
+  if (FstError e = trim_lattices(S.E, out->v.status, *Lt, num, stream); e != FST_OK) return e;
+  drain.done = true;  // (trim_lattices synchronised it)
+  Lt->input = std::move(st);
+  S.lat = std::move(Lt);
+  S.keep = std::move(out);
+  return FST_OK;
+}
+
 FstError run_lattice_arena(DeviceEngine::Lease& E, DeviceFst& D, const ChainInput& in,
                            const GraphInput* lhs, uint32_t lattice_flags, uint64_t est_states,
                            uint64_t est_arcs, std::unique_ptr<LatShard>* lat,
@@ -899,6 +1042,10 @@ FstError run_lattice_arena(DeviceEngine::Lease& E, DeviceFst& D, const ChainInpu
     for (uint32_t i = 0; i < num; ++i) full |= status[i] == kPathOutputFull;
     // the last attempt's result stands: items still OUTPUT_FULL keep that status
     if (!full || attempt + 1 == kAttempts) {
+      if (lattice_flags & FST_LATTICE_CONNECT) {
+        L->connect = true;
+        if (FstError e = trim_lattices(E, out->v.status, *L, num, stream); e != FST_OK) return e;
+      }
       *lat = std::move(L);
       *keep = std::move(out);
       return FST_OK;

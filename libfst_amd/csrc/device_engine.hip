@@ -2986,11 +2986,13 @@ hipError_t DeviceEngine::compact_lattices_count(const int32_t* status, const Lat
 }
 
 hipError_t DeviceEngine::compact_lattices(const LatticeOutDev& lat, uint32_t num,
-                                          const LatticeCsrDev& csr, hipStream_t stream) {
+                                          const LatticeCsrDev& csr, hipStream_t stream,
+                                          const LatTrimDev* trim) {
   HIP_TRY(hipSetDevice(dev_));
   const uint64_t* arc_base = (const uint64_t*)scratch(kLatArcBase, ((size_t)num + 1) * 8 + 16);
   if (!arc_base) return hipErrorOutOfMemory;
   const uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(num, (uint32_t)num_cus_ * 32));
+  if (trim) return launch_trim_gather(lat, *trim, arc_base, csr, num, grid, stream);
   return launch_lattice_gather(lat, arc_base, csr, num, grid, stream);
 }
 

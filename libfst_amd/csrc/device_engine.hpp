@@ -287,6 +287,23 @@ struct LatticeCsrDev {
   uint32_t* next;
   uint64_t state_cap, arc_cap;
 };
+// The lattice trim's workspace (kernels/lattice_trim.hpp): connect of every item
+// of an arena before its compaction.
+enum : uint32_t { kTrimCtrList = 0, kTrimCtrSweep = 1, kTrimCtrLinear = 2, kTrimCtrWords = 4 };
+struct LatTrimDev {
+  uint32_t* mark;    // [state_cap] bit 0 coaccessible, bit 1 accessible; then the new ids
+  uint32_t* queue;   // [state_cap] the frontier BFS's queue (accessibility, the linear tier)
+  uint32_t* roff;    // [state_cap] the linear tier: the item's reverse CSR ...
+  uint32_t* rcur;    // [state_cap]     ... its fill cursors ...
+  uint32_t* rsrc;    // [arc_cap]       ... and the arcs' sources
+  uint32_t* list;    // [num] items the sweep tier handed on
+  uint32_t* ctr;     // [kTrimCtrWords] the list's length, items settled per tier
+  unsigned long long* tot;  // [4] states before / after, arcs before / after
+  const uint32_t* start;    // [num] the items' starts; null: 0 (compose output)
+  uint32_t sweeps;          // the sweep budget (FSTAMD_TRIM_SWEEPS)
+  uint32_t access;          // 1: mark holds the accessibility pass's result
+  uint32_t aoff_skew;       // item i's arc offsets start at aoff[spos + aoff_skew * i]
+};
 
 // Chain inputs (batch API) or one general lhs FST (single-call C ABI).
 struct ChainInput {
@@ -467,6 +484,23 @@ hipError_t launch_lattice_count(const int32_t* status, const LatItem* item, uint
 hipError_t launch_lattice_gather(const LatticeOutDev& arena, const uint64_t* arc_base,
                                  const LatticeCsrDev& csr, uint32_t num, uint32_t grid,
                                  hipStream_t stream);
+// ---- lattice trim (lattice_trim.hip, kernels/lattice_trim.hpp): connect on the arena ----
+hipError_t launch_trim_stage(const LhsDesc* desc, uint32_t num, LatItem* item, int32_t* status,
+                             uint32_t* start, hipStream_t stream);
+hipError_t launch_trim_access(const LatticeOutDev& arena, const LatTrimDev& t,
+                              const int32_t* status, uint32_t num, uint32_t grid,
+                              hipStream_t stream);
+hipError_t launch_trim_sweep(const LatticeOutDev& arena, const LatTrimDev& t,
+                             const int32_t* status, uint32_t num, uint32_t grid,
+                             hipStream_t stream);
+hipError_t launch_trim_linear(const LatticeOutDev& arena, const LatTrimDev& t,
+                              const int32_t* status, uint32_t grid, hipStream_t stream);
+hipError_t launch_trim_finalize(const LatticeOutDev& arena, const LatTrimDev& t,
+                                const int32_t* status, uint32_t num, uint32_t grid,
+                                hipStream_t stream);
+hipError_t launch_trim_gather(const LatticeOutDev& arena, const LatTrimDev& t,
+                              const uint64_t* arc_base, const LatticeCsrDev& csr, uint32_t num,
+                              uint32_t grid, hipStream_t stream);
 // On-device preparation of a device-resident batch (kernels/lhs_prepare.hpp; lhs_batch.hip
 // holds the instances).  In: the caller's arrays in FstLhsBatch's layout, all device memory,
 // and their two extents as the host read them.  Out: descriptors, local arc offsets
@@ -639,8 +673,9 @@ class DeviceEngine {
                                     hipStream_t stream);
   // Step 2 (after step 1 on the same engine; needed within csr's capacities): start, finals,
   // global arc offsets with the closing entry, and the arcs.  Asynchronous on `stream`.
+  // `trim` (a trimmed arena: host::trim_lattices): the filtering gather instead.
   hipError_t compact_lattices(const LatticeOutDev& lat, uint32_t num, const LatticeCsrDev& csr,
-                              hipStream_t stream);
+                              hipStream_t stream, const LatTrimDev* trim = nullptr);
   // Output tape of each path of a finished stage as the next stage's chain inputs
   // (printOutputString + compileString on device): next_labels = the path's non-epsilon
   // olabels.  A string whose status is not OK, or whose output has a label > 256, gets

@@ -155,6 +155,12 @@ struct LatShard {
   std::unique_ptr<DevBuf> item, afin, aaoff, ail, aol, aw, anext, cursor;  // the arena
   LatticeOutDev arena{};
   std::unique_ptr<DevBuf> status, soff, start, fin, aoffs, il, ol, w, next;  // compacted
+  // FST_LATTICE_CONNECT / fst_connect_lhs_batch: the trim's workspace (trim_lattices), alive
+  // until the filtering gather has run; `input`: the staged items a stand-alone arena points into
+  bool connect = false;
+  std::unique_ptr<DevBuf> tmark, tqueue, troff, trcur, trsrc, tlist, tctr, tstart;
+  LatTrimDev trim{};
+  std::shared_ptr<void> input;
 };
 
 struct Shard {
@@ -226,6 +232,14 @@ FstError run_lattice_arena(DeviceEngine::Lease& E, DeviceFst& D, const ChainInpu
                            const GraphInput* lhs, uint32_t lattice_flags, uint64_t est_states,
                            uint64_t est_arcs, std::unique_ptr<LatShard>* lat,
                            std::unique_ptr<DevOut>* keep);
+// Connect of every OK item of L's arena (kernels/lattice_trim.hpp): the sweep tier, the linear
+// tier for what it handed on, then the map and the trimmed counts in LatItem.  With L.tstart
+// (the stand-alone entry) the accessibility pass runs first.  Adds its launches and kernel time
+// to t_last_stats; synchronises `stream`.
+FstError trim_lattices(DeviceEngine::Lease& E, const int32_t* status, LatShard& L, uint32_t num,
+                       hipStream_t stream);
+// fst_connect_lhs_batch's shard: the items staged as run_lhs_shard stages them, then trimmed.
+FstError run_connect_shard(Shard& S, const FstLhsBatch& L);
 FstError run_pipelined(int dev, FrozenFst& b, const uint32_t* labels, const uint64_t* offsets,
                        uint32_t num, uint32_t n, int semantics, uint32_t parts,
                        FstBatchResult* out);

@@ -84,6 +84,7 @@ class FstDeviceBatch(C.Structure):
 
 
 FST_LATTICE_PROJECT_OUTPUT = 1
+FST_LATTICE_CONNECT = 4  # (bit 1 is not assigned)
 
 
 class FstLatticeBatch(C.Structure):
@@ -162,6 +163,9 @@ SIGNATURES = {
         C.c_int, [_u64, C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstLatticeBatch)]),
     "fst_lattice_batch_free": (None, [C.POINTER(FstLatticeBatch)]),
+    "fst_connect_lhs_batch": (
+        C.c_int, [C.POINTER(FstLhsBatch), C.POINTER(FstBatchOptions),
+                  C.POINTER(FstLatticeBatch)]),
     "fst_device_compose_frozen": (
         C.c_int, [_u64, _P, _P, _u32, _u32, _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceLattices), C.POINTER(_u64), _P]),
@@ -554,17 +558,23 @@ class LatticeBatch:
         return int(self.start[i]), self.final_weights[s0:s1].tolist(), arcs
 
 
+def _lattice_flags(project_output: bool, connect: bool) -> int:
+    return ((FST_LATTICE_PROJECT_OUTPUT if project_output else 0) |
+            (FST_LATTICE_CONNECT if connect else 0))
+
+
 def compose_frozen_batch(b: Fst, labels, offsets, project_output: bool = False, device: int = -1,
-                         devices=None, shards: int = 0) -> LatticeBatch:
+                         devices=None, shards: int = 0, connect: bool = False) -> LatticeBatch:
     """fst_compose_frozen for a batch of chains (fst_compose_frozen_batch): item i is the
-    lattice fst_compose_frozen(compile(labels of string i), b) returns, bit for bit."""
+    lattice fst_compose_frozen(compile(labels of string i), b) returns, bit for bit; with
+    `connect` (FST_LATTICE_CONNECT) its connect: the states that reach a final state."""
     labels = np.ascontiguousarray(labels, dtype=np.uint32)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     opts = batch_options(device, FST_SEM_LAZY, devices, shards)
     res = FstLatticeBatch()
     rc = lib().fst_compose_frozen_batch(b.h, labels.ctypes.data, offsets.ctypes.data,
                                         len(offsets) - 1,
-                                        FST_LATTICE_PROJECT_OUTPUT if project_output else 0,
+                                        _lattice_flags(project_output, connect),
                                         C.byref(opts), C.byref(res))
     if rc != FST_OK:
         raise RuntimeError(f"fst_compose_frozen_batch failed: {rc}")
@@ -572,16 +582,31 @@ def compose_frozen_batch(b: Fst, labels, offsets, project_output: bool = False, 
 
 
 def compose_frozen_lhs_batch(b: Fst, lhs: LhsBatch, project_output: bool = False,
-                             device: int = -1, devices=None, shards: int = 0) -> LatticeBatch:
+                             device: int = -1, devices=None, shards: int = 0,
+                             connect: bool = False) -> LatticeBatch:
     """The same for a batch of general lhs (fst_compose_frozen_lhs_batch)."""
     opts = batch_options(device, FST_SEM_LAZY, devices, shards)
     res = FstLatticeBatch()
     cs = lhs.c_struct()
     rc = lib().fst_compose_frozen_lhs_batch(b.h, C.byref(cs),
-                                            FST_LATTICE_PROJECT_OUTPUT if project_output else 0,
+                                            _lattice_flags(project_output, connect),
                                             C.byref(opts), C.byref(res))
     if rc != FST_OK:
         raise RuntimeError(f"fst_compose_frozen_lhs_batch failed: {rc}")
+    return LatticeBatch(res)
+
+
+def connect_lhs_batch(lhs: LhsBatch, device: int = -1, devices=None,
+                      shards: int = 0) -> LatticeBatch:
+    """Connect (trim) of every item of an lhs batch (fst_connect_lhs_batch): the states that are
+    reachable from the start and reach a final state, renumbered in their order; every item is
+    FST_PATH_OK and NaN weights are copied."""
+    opts = batch_options(device, FST_SEM_LAZY, devices, shards)
+    res = FstLatticeBatch()
+    cs = lhs.c_struct()
+    rc = lib().fst_connect_lhs_batch(C.byref(cs), C.byref(opts), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_connect_lhs_batch failed: {rc}")
     return LatticeBatch(res)
 
 
