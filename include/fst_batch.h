@@ -320,6 +320,47 @@ void fst_lattice_batch_free(FstLatticeBatch* r);
 FstError fst_connect_lhs_batch(const FstLhsBatch* lhs, const FstBatchOptions* opts,
                                FstLatticeBatch* out);
 
+/* Shortest path of every item of an lhs batch, with no compose: the 1-best of a recogniser's
+ * lattices, or of a lattice batch the caller has rescored (LM scores added to the arc weights, a
+ * bias on some olabels, a penalty on finals).  Item i is fst_shortest_path(lhs_i, n)
+ * (src/ops/shortest-path.zig:18-139), bit for bit, as a status and a 1-best chain in the
+ * FstBatchResult.  Per item, in the single call's order (:21-24):
+ *   no start (an item of zero states has none) or n == 0       FST_PATH_EMPTY
+ *   any other n != 1                                           FST_PATH_ERROR_N
+ *   a NaN arc or final weight in the item                      FST_PATH_UNSUPPORTED (the single
+ *       call returns an invalid handle there; the compose entries' rule)
+ *   no final state reachable, or the backtrace does not end
+ *       at the start (:105, :120)                              FST_PATH_EMPTY
+ *   a back-pointer cycle (the reference would not terminate)   FST_PATH_CYCLE
+ *   otherwise                                                  FST_PATH_OK
+ * An OK path's arcs are the item's own arcs, ilabel, olabel and weight copied bit for bit;
+ * final_weights[i] is the final weight of the chosen final state, copied; a path of zero arcs
+ * (the start is the best final) is FST_PATH_OK with a length of 0.
+ * A non-OK item of an FstLatticeBatch owns zero states, so here it comes out FST_PATH_EMPTY:
+ * callers feeding &r.fsts should read r.status first.
+ * The same validator as the other lhs entries runs first (a failed check: FST_INVALID_ARG with
+ * *out zeroed; also a null lhs / out, unknown opts->flags).  num_fsts == 0 gives the empty OK
+ * result.  There is no rhs and opts->semantics is ignored.  FST_BATCH_DEVICES shards by arcs + 1
+ * per item; a sharded result is byte-identical to a one-shard run.  The result is an ordinary
+ * FstBatchResult (fst_batch_result_free, fst_batch_result_to_text).  fst_last_launch_stats
+ * reports engine 12. */
+FstError fst_shortest_path_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
+                                     const FstBatchOptions* opts, FstBatchResult* out);
+
+/* Device-resident: d_lhs as for fst_device_compose_shortest_path_lhs (a host struct of device
+ * pointers, trusted extents, per-item validation by the prepare kernel: an item that fails it
+ * reports FST_PATH_UNSUPPORTED and is never traversed; state_offsets decreasing anywhere makes
+ * every item FST_PATH_UNSUPPORTED), out as for every FstDeviceBatch producer: the arena is the
+ * caller's, items that do not fit report FST_PATH_OUTPUT_FULL, *arc_cursor ends at what the
+ * batch needs (the total states of the batch always suffice), and the result chains into
+ * fst_device_project_output, fst_device_compose_shortest_path and fst_device_emit_text.  So
+ * chains -> lattices (fst_device_compose_frozen) -> the caller's rescoring kernel -> 1-best ->
+ * text never leaves the device.  The call SYNCHRONISES `stream`.  Engine 12; `launches` counts
+ * the two preparation kernels too. */
+FstError fst_device_shortest_path_lhs(const FstLhsBatch* d_lhs, uint32_t n,
+                                      const FstBatchOptions* opts, const FstDeviceBatch* out,
+                                      void* stream);
+
 /* The device-resident form, chains in and lattices out, so that a cascade never leaves the
  * device.  Every pointer in `out` is device memory on opts->device, in FstLhsBatch's layout: a
  * host-side FstLhsBatch holding those pointers goes straight into
@@ -444,7 +485,10 @@ typedef struct {
                                    9 = lhs batch, eager (general BFS tiers, 1-best in kernel),
                                    10 = lattice batch (general BFS tiers, lattice emission;
                                         with FST_LATTICE_CONNECT the trim kernels too),
-                                   11 = fst_connect_lhs_batch (the lattice trim alone) */
+                                   11 = fst_connect_lhs_batch (the lattice trim alone),
+                                   12 = fst_shortest_path_lhs_batch and
+                                        fst_device_shortest_path_lhs (one wave per lattice,
+                                        frontier and heap-replay tiers behind it) */
     uint32_t grid;              /* workgroups of the dominant kernel */
 } FstLaunchStats;
 FstError fst_last_launch_stats(FstLaunchStats* out);

@@ -211,6 +211,30 @@ bool lhs_pipeline_args(const FstHandle* stages, uint32_t num_stages, const FstLh
   return true;
 }
 
+// The prepare kernel's inputs for a device-resident lhs batch: the caller's device pointers and
+// the two extents of their arrays (the last state offset, the last arc offset), which the host
+// reads and trusts (fst_batch.h); the prepare kernel checks every other offset against them.
+FstError device_lhs_extents(const FstLhsBatch* d_lhs, hipStream_t s, LhsPrepIn* in) {
+  const uint32_t num = d_lhs->num_fsts;
+  in->num = num;
+  in->state_offsets = d_lhs->state_offsets;
+  in->start = d_lhs->start;
+  in->final_w = d_lhs->final_weights;
+  in->arc_offsets = d_lhs->arc_offsets;
+  in->arc_ol = d_lhs->olabels;
+  in->arc_w = d_lhs->weights;
+  in->arc_next = d_lhs->nextstates;
+  if (num) {
+    if (!read_u64(&in->total_states, d_lhs->state_offsets + num, s)) return FST_OOM;
+    if (!read_u64(&in->total_arcs, d_lhs->arc_offsets + in->total_states, s)) return FST_OOM;
+  }
+  if ((in->total_states && !d_lhs->final_weights) ||
+      (in->total_arcs &&
+       (!d_lhs->ilabels || !d_lhs->olabels || !d_lhs->weights || !d_lhs->nextstates)))
+    return FST_INVALID_ARG;
+  return FST_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -418,6 +442,26 @@ FstError fst_connect_lhs_batch(const FstLhsBatch* lhs, const FstBatchOptions* op
   return call.close(e, "fst_connect_lhs_batch", out, fst_lattice_batch_free);
 }
 
+// fst_shortest_path of every item of an lhs batch: no rhs, no compose; the items are staged as
+// the lhs entries stage them and reduced to their 1-best paths in place (run_sp_shard).
+FstError fst_shortest_path_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
+                                     const FstBatchOptions* opts, FstBatchResult* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!lhs_batch_valid(lhs) || !flags_ok(opts)) return FST_INVALID_ARG;
+  const uint32_t num = lhs->num_fsts;
+  if (num == 0) return empty_result(out);
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  std::vector<double> cost(call.nsh > 1 ? num : 0);
+  for (size_t i = 0; i < cost.size(); ++i)
+    cost[i] = (double)(lhs->arc_offsets[lhs->state_offsets[i + 1]] -
+                       lhs->arc_offsets[lhs->state_offsets[i]]) + 1.0;
+  const FstError e = run_sharded(
+      call.devices, call.nsh, num, cost, [&](Shard& S) { return run_sp_shard(S, *lhs, n); }, out);
+  return call.close(e, "fst_shortest_path_lhs_batch", out, fst_batch_result_free);
+}
+
 void fst_lattice_batch_free(FstLatticeBatch* r) {
   if (!r) return;
   pin_release(r->status);
@@ -527,24 +571,7 @@ FstError fst_device_compose_shortest_path_lhs(FstHandle b_handle, const FstLhsBa
   // every return waits for what the call queued: the engine's workspaces are its own again
   StreamDrain drain{{s}};
   LhsPrepIn in{};
-  in.num = num;
-  in.state_offsets = d_lhs->state_offsets;
-  in.start = d_lhs->start;
-  in.final_w = d_lhs->final_weights;
-  in.arc_offsets = d_lhs->arc_offsets;
-  in.arc_ol = d_lhs->olabels;
-  in.arc_w = d_lhs->weights;
-  in.arc_next = d_lhs->nextstates;
-  // the extents of the caller's arrays, trusted (fst_batch.h): the prepare kernel checks
-  // every other offset against them
-  if (num) {
-    if (!read_u64(&in.total_states, d_lhs->state_offsets + num, s)) return FST_OOM;
-    if (!read_u64(&in.total_arcs, d_lhs->arc_offsets + in.total_states, s)) return FST_OOM;
-  }
-  if ((in.total_states && !d_lhs->final_weights) ||
-      (in.total_arcs &&
-       (!d_lhs->ilabels || !d_lhs->olabels || !d_lhs->weights || !d_lhs->nextstates)))
-    return FST_INVALID_ARG;
+  if (FstError e = device_lhs_extents(d_lhs, s, &in); e != FST_OK) return e;
   LhsPrepared p;
   if (E->prepare_lhs(*D, in, s, &p) != hipSuccess) return FST_OOM;
   if (p.max_outdeg >= (1u << 30)) return FST_OOM;  // the lazy per-pop table is 2 * deg + 2 entries
@@ -570,6 +597,53 @@ FstError fst_device_compose_shortest_path_lhs(FstHandle b_handle, const FstLhsBa
   // (run_lhs_batch waited for its last tier: with stats it ends on an event of the stream;
   // an empty batch queued one memset, which the drain still waits for)
   drain.done = num != 0;
+  return FST_OK;
+}
+
+// fst_shortest_path of a device-resident lhs batch: prepared as above but with no rhs (the
+// items' flags are their own), then DeviceEngine::run_sp_batch into the caller's arena.
+FstError fst_device_shortest_path_lhs(const FstLhsBatch* d_lhs, uint32_t n,
+                                      const FstBatchOptions* opts, const FstDeviceBatch* o,
+                                      void* stream) {
+  if (!o || !d_lhs || !flags_ok(opts)) return FST_INVALID_ARG;
+  const uint32_t num = d_lhs->num_fsts;
+  if (num && (!d_lhs->state_offsets || !d_lhs->start || !d_lhs->arc_offsets))
+    return FST_INVALID_ARG;
+  if (!o->arc_cursor || (num && (!o->status || !o->path_len || !o->path_offset || !o->final_weight)))
+    return FST_INVALID_ARG;
+  if (!gpu_available()) return FST_INVALID_ARG;
+  DeviceRestore_ restore;
+  const int dev = opts && opts->device >= 0 ? opts->device : current_device();
+  if (dev < 0 || hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  DeviceEngine::Lease E = DeviceEngine::acquire(dev);
+  if (!E) return FST_INVALID_ARG;
+  const hipStream_t s = E.use((hipStream_t)stream);
+  // every return waits for what the call queued: the engine's workspaces are its own again
+  StreamDrain drain{{s}};
+  LhsPrepIn in{};
+  if (FstError e = device_lhs_extents(d_lhs, s, &in); e != FST_OK) return e;
+  LhsPrepared p;
+  if (E->prepare_lhs(in, s, &p) != hipSuccess) return FST_OOM;
+  ChainInput ci{};
+  ci.lhs_desc = p.desc;
+  ci.num_strings = num;
+  GraphInput g{};
+  g.state_off = p.state_off;
+  g.final_w = d_lhs->final_weights;
+  g.arc_w = d_lhs->weights;
+  g.arc_il = d_lhs->ilabels;
+  g.arc_ol = d_lhs->olabels;
+  g.arc_next = d_lhs->nextstates;
+  g.start = kNoState;
+  g.max_outdeg = p.max_outdeg;
+  LaunchStats st;
+  LhsRoute route;
+  if (E->run_sp_batch(ci, g, in.total_states, in.total_arcs, n, p.items_nonneg, p.num_nonneg,
+                      p.items_replay, p.num_replay, dev_out(o), s, &st, &route) != hipSuccess)
+    return FST_OOM;
+  st.launches += p.launches;
+  t_last_stats = st;
+  drain.done = true;  // (run_sp_batch synchronised the stream)
   return FST_OK;
 }
 

@@ -817,6 +817,40 @@ FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n,
       &h, &S.keep);
 }
 
+// One shard of fst_shortest_path_lhs_batch: the staged items through DeviceEngine::run_sp_batch,
+// which reads the staged block in place.  An OK path has at most num_states - 1 arcs (a longer
+// back-pointer walk is a cycle), so an arena of the shard's states is never too small: no
+// OUTPUT_FULL, no rerun.
+FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n) {
+  const int dev = S.E->dev();
+  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  const hipStream_t stream = S.E.stream();
+  const uint32_t num = S.s1 - S.s0;
+  LhsStaged st;
+  // every return drains the stream before the staged blocks and the arena go back to their pools
+  StreamDrain drain{{stream}};
+  if (FstError e = stage_lhs_items(S, nullptr, L, stream, &st); e != FST_OK) return e;
+  auto out = std::make_unique<DevOut>(num, std::max<uint64_t>(st.num_states, 1));
+  if (!out->ok()) return FST_OOM;
+  if (t_prof) t_prof->lap(1);
+  LaunchStats ls;
+  LhsRoute route;
+  const hipError_t err =
+      S.E->run_sp_batch(st.in, st.g, st.num_states, st.num_arcs, n, st.items_nonneg,
+                        st.num_nonneg, st.items_replay, st.num_replay, out->v, stream, &ls, &route);
+  if (t_prof) {
+    t_prof->lap(2);
+    ++t_prof->runs;
+  }
+  if (err != hipSuccess) {
+    std::fprintf(stderr, "[libfst_amd] lattice shortest path failed: %s\n", hipGetErrorString(err));
+    return FST_OOM;
+  }
+  t_last_stats = ls;
+  S.keep = std::move(out);
+  return FST_OK;  // (the drain: run_sp_batch synchronised, nothing is left to wait for)
+}
+
 // ---- Lattice shards ---------------------------------------------------------------------
 
 bool alloc_lattice_result(FstLatticeBatch* out, uint32_t num, uint64_t states, uint64_t arcs) {

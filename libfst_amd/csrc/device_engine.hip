@@ -460,6 +460,15 @@ enum Scratch : size_t {
   kLatCntStates,
   kLatCntArcs,
   kLatArcBase,
+  kSpKey,
+  kSpBack,
+  kSpMark,
+  kSpFa,
+  kSpFb,
+  kSpHeap,
+  kSpSettled,
+  kSpList,
+  kSpCtr,
   kNumScratch
 };
 
@@ -2996,13 +3005,122 @@ hipError_t DeviceEngine::compact_lattices(const LatticeOutDev& lat, uint32_t num
   return launch_lattice_gather(lat, arc_base, csr, num, grid, stream);
 }
 
+// ---- lattice shortest path (lattice_sp.hip holds the kernels) ---------------------------
+
+hipError_t DeviceEngine::run_sp_batch(const ChainInput& in, const GraphInput& lhs,
+                                      uint64_t total_states, uint64_t total_arcs, uint32_t n,
+                                      const uint32_t* items_nonneg, uint32_t num_nonneg,
+                                      const uint32_t* items_replay, uint32_t num_replay,
+                                      const BatchOutDev& out, hipStream_t stream,
+                                      LaunchStats* stats, LhsRoute* route) {
+  HIP_TRY(hipSetDevice(dev_));
+  const uint32_t num = in.num_strings;
+  HIP_TRY(hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), stream));
+  if (stats) {
+    stats->engine = 12;
+    stats->grid = 0;
+    stats->launches = 0;
+  }
+  if (num == 0) return hipStreamSynchronize(stream);
+  if ((uint64_t)num_nonneg + num_replay != num) return hipErrorInvalidValue;
+  uint32_t sweeps = 4;  // ids that rise along arcs settle in one; tests: FSTAMD_SP_SWEEPS
+  if (const char* e = std::getenv("FSTAMD_SP_SWEEPS"))
+    if (*e) sweeps = (uint32_t)std::min<unsigned long long>(std::strtoull(e, nullptr, 10), 1u << 20);
+  const uint32_t cap = grid_cap("FSTAMD_GRAPH_GRID");
+  const uint32_t cus = (uint32_t)std::max(num_cus_, 1);
+  const size_t sw = ((size_t)total_states + 4) * 4;
+  LatSpDev p{};
+  p.desc = in.lhs_desc;
+  p.state_off = lhs.state_off;
+  p.final_w = lhs.final_w;
+  p.arc_next = lhs.arc_next;
+  p.arc_il = lhs.arc_il;
+  p.arc_ol = lhs.arc_ol;
+  p.arc_w = lhs.arc_w;
+  p.key = (unsigned long long*)scratch(kSpKey, 2 * sw);
+  p.back = (unsigned long long*)scratch(kSpBack, 2 * sw);
+  p.list = (uint32_t*)scratch(kSpList, (size_t)num * 4);
+  p.ctr = (uint32_t*)scratch(kSpCtr, kSpCtrWords * 4);
+  if (!p.key || !p.back || !p.list || !p.ctr) return hipErrorOutOfMemory;
+  if (num_replay) {
+    p.heap = (SpHeapEnt*)scratch(kSpHeap, ((size_t)total_arcs + num) * 16);
+    p.settled = (uint8_t*)scratch(kSpSettled, (size_t)total_states + 16);
+    if (!p.heap || !p.settled) return hipErrorOutOfMemory;
+  }
+  p.sweeps = sweeps;
+  p.n_best = n;
+  p.wd_ticks = watchdog_ticks();
+  // every item starts as INTERNAL: an item no kernel finished can never read as a result
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out.status, kPathInternal, num, stream));
+  HIP_TRY(hipMemsetAsync(p.ctr, 0, kSpCtrWords * 4, stream));
+  uint32_t ctr[kSpCtrWords] = {};
+  uint32_t launches = 0, grid_max = 0;
+  HIP_TRY(timed(stats, stream, [&]() -> hipError_t {
+    if (num_nonneg) {
+      const uint32_t g = std::max<uint32_t>(1, std::min({num_nonneg, cus * 32, cap}));
+      HIP_TRY(launch_sp_wave(p, items_nonneg, num_nonneg, out, g, stream));
+      grid_max = std::max(grid_max, g);
+      ++launches;
+    }
+    if (num_replay) {
+      const uint32_t g = std::max<uint32_t>(1, std::min({num_replay, cus * 32, cap}));
+      HIP_TRY(launch_sp_replay(p, items_replay, num_replay, out, g, stream));
+      grid_max = std::max(grid_max, g);
+      ++launches;
+    }
+    HIP_TRY(copy_sync(ctr, p.ctr, sizeof(ctr), hipMemcpyDeviceToHost, stream));
+    const uint32_t handed = ctr[kSpCtrList];
+    if (handed > num_nonneg) return hipErrorUnknown;  // (the list holds an item at most once)
+    if (handed == 0) return hipSuccess;
+    p.mark = (uint32_t*)scratch(kSpMark, sw);
+    p.fa = (uint32_t*)scratch(kSpFa, sw);
+    p.fb = (uint32_t*)scratch(kSpFb, sw);
+    if (!p.mark || !p.fa || !p.fb) return hipErrorOutOfMemory;
+    const uint32_t g = std::max<uint32_t>(1, std::min({handed, cus * 8, cap}));
+    HIP_TRY(launch_sp_frontier(p, out, g, stream));
+    ++launches;
+    return copy_sync(ctr, p.ctr, sizeof(ctr), hipMemcpyDeviceToHost, stream);
+  }));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if ((uint64_t)ctr[kSpCtrWave] + ctr[kSpCtrFrontier] + ctr[kSpCtrReplay] != num)
+    return hipErrorUnknown;  // (every item is finished by exactly one tier)
+  if (stats) {
+    stats->grid = grid_max;
+    stats->launches = launches;
+  }
+  if (std::getenv("FSTAMD_ROUTE_LOG"))
+    std::fprintf(stderr,
+                 "[libfst_amd route] lattice sp: items %u | wave %u frontier %u replay %u | "
+                 "%.3f ms\n",
+                 num, ctr[kSpCtrWave], ctr[kSpCtrFrontier], ctr[kSpCtrReplay],
+                 stats ? stats->kernel_ms : 0.0);
+  if (route) {
+    *route = LhsRoute();
+    route->t[0] = ctr[kSpCtrWave];
+    route->t[1] = ctr[kSpCtrFrontier];
+    route->replay = ctr[kSpCtrReplay];
+    route->tiers_run = launches;
+  }
+  return hipSuccess;
+}
+
 hipError_t DeviceEngine::prepare_lhs(const DeviceFst& rhs, LhsPrepIn in, hipStream_t stream,
                                      LhsPrepared* prepared) {
+  in.base_flags = (rhs.nan ? kLhsNaN : 0u) | (rhs.nonneg ? 0u : kLhsReplay);
+  return prepare_lhs_flags(in, stream, prepared);
+}
+
+hipError_t DeviceEngine::prepare_lhs(LhsPrepIn in, hipStream_t stream, LhsPrepared* prepared) {
+  in.base_flags = 0;
+  return prepare_lhs_flags(in, stream, prepared);
+}
+
+hipError_t DeviceEngine::prepare_lhs_flags(LhsPrepIn in, hipStream_t stream,
+                                           LhsPrepared* prepared) {
   HIP_TRY(hipSetDevice(dev_));
   *prepared = LhsPrepared();
   const uint32_t num = in.num;
   if (num == 0) return hipStreamSynchronize(stream);
-  in.base_flags = (rhs.nan ? kLhsNaN : 0u) | (rhs.nonneg ? 0u : kLhsReplay);
   LhsPrepOut out{};
   out.desc = (LhsDesc*)scratch(kLhsPrepDesc, (size_t)num * sizeof(LhsDesc));
   // one extra offset word per item (lhs_item: the item's words start at state_base + i)

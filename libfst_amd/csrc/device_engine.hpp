@@ -304,6 +304,32 @@ struct LatTrimDev {
   uint32_t access;          // 1: mark holds the accessibility pass's result
   uint32_t aoff_skew;       // item i's arc offsets start at aoff[spos + aoff_skew * i]
 };
+// The lattice shortest path's inputs and workspace (kernels/lattice_sp.hpp):
+// fst_shortest_path of every item of an lhs batch, the batch's CSR read in place.
+enum : uint32_t { kSpCtrList = 0, kSpCtrWave = 1, kSpCtrFrontier = 2, kSpCtrReplay = 3,
+                  kSpCtrWords = 4 };
+struct SpHeapEnt;
+struct LatSpDev {
+  const struct LhsDesc* desc;  // [num]
+  const uint32_t* state_off;   // the batch's arrays, as GraphInput holds them for a batch
+  const double* final_w;
+  const uint32_t* arc_next;
+  const uint32_t* arc_il;
+  const uint32_t* arc_ol;
+  const double* arc_w;
+  unsigned long long* key;     // [states] okey of the distance
+  unsigned long long* back;    // [states] (source << 32) | arc index of the back-pointer
+  uint32_t* mark;              // [states] the frontier tier: round stamps ...
+  uint32_t* fa;                // [states]     ... and its two frontiers
+  uint32_t* fb;
+  SpHeapEnt* heap;             // [arcs + num] the replay tier: item i's heap at arc_base + i
+  uint8_t* settled;            // [states]     ... and its settled flags
+  uint32_t* list;              // [num] items the wave tier handed on
+  uint32_t* ctr;               // [kSpCtrWords] the list's length, items finished per tier
+  uint32_t sweeps;             // the wave tier's budget (FSTAMD_SP_SWEEPS)
+  uint32_t n_best;
+  unsigned long long wd_ticks;
+};
 
 // Chain inputs (batch API) or one general lhs FST (single-call C ABI).
 struct ChainInput {
@@ -501,6 +527,13 @@ hipError_t launch_trim_finalize(const LatticeOutDev& arena, const LatTrimDev& t,
 hipError_t launch_trim_gather(const LatticeOutDev& arena, const LatTrimDev& t,
                               const uint64_t* arc_base, const LatticeCsrDev& csr, uint32_t num,
                               uint32_t grid, hipStream_t stream);
+// ---- lattice shortest path (lattice_sp.hip, kernels/lattice_sp.hpp) ----
+hipError_t launch_sp_wave(const LatSpDev& p, const uint32_t* items, uint32_t count,
+                          const BatchOutDev& out, uint32_t grid, hipStream_t stream);
+hipError_t launch_sp_frontier(const LatSpDev& p, const BatchOutDev& out, uint32_t grid,
+                              hipStream_t stream);
+hipError_t launch_sp_replay(const LatSpDev& p, const uint32_t* items, uint32_t count,
+                            const BatchOutDev& out, uint32_t grid, hipStream_t stream);
 // On-device preparation of a device-resident batch (kernels/lhs_prepare.hpp; lhs_batch.hip
 // holds the instances).  In: the caller's arrays in FstLhsBatch's layout, all device memory,
 // and their two extents as the host read them.  Out: descriptors, local arc offsets
@@ -545,7 +578,8 @@ struct LhsPrepared {
 // What a batch of general lhs took which way (FSTAMD_ROUTE_LOG, tests): items that entered
 // each tier.  Eager: t[0..3] = tiny128, tiny256, tier 0, tiers 1+ (summed); replay = items on
 // the heap-replay route (they appear in t[2..3] too).  Lazy: t[k] = items that entered the
-// table tier of 1024 << 4k tuples.
+// table tier of 1024 << 4k tuples.  run_sp_batch: t[0..1] = items the wave / frontier tier
+// finished.
 struct LhsRoute {
   uint32_t t[8] = {};
   uint32_t replay = 0;
@@ -653,6 +687,20 @@ class DeviceEngine {
   // invalid.  Synchronises `stream`.  in.base_flags is set here from the rhs.
   hipError_t prepare_lhs(const DeviceFst& rhs, LhsPrepIn in, hipStream_t stream,
                          LhsPrepared* prepared);
+  // The same with no rhs (fst_device_shortest_path_lhs): in.base_flags is 0, so an item's flags
+  // are the item's own.
+  hipError_t prepare_lhs(LhsPrepIn in, hipStream_t stream, LhsPrepared* prepared);
+  // fst_shortest_path of every item of an lhs batch (fst_shortest_path_lhs_batch; kernels/
+  // lattice_sp.hpp): in / lhs / the two item lists as for run_lhs_batch, total_states /
+  // total_arcs the batch's extents (they size the workspaces).  The wave tier takes the
+  // non-negative items and hands what its sweep budget (FSTAMD_SP_SWEEPS) does not settle to the
+  // frontier tier; the replay tier takes the others.  Items the arena cannot hold end
+  // OUTPUT_FULL, the cursor at what the batch needs.  Synchronises `stream`.
+  hipError_t run_sp_batch(const ChainInput& in, const GraphInput& lhs, uint64_t total_states,
+                          uint64_t total_arcs, uint32_t n, const uint32_t* items_nonneg,
+                          uint32_t num_nonneg, const uint32_t* items_replay,
+                          uint32_t num_replay, const BatchOutDev& out, hipStream_t stream,
+                          LaunchStats* stats, LhsRoute* route);
   // fst_compose_frozen: the whole lattice of one general lhs (kernels/eager_bfs.hpp), on
   // `stream` (synchronised: the lattice is downloaded).
   hipError_t compose_lattice(const DeviceFst& rhs, const GraphInput& lhs, HostLattice* lat,
@@ -818,6 +866,8 @@ class DeviceEngine {
                            const BatchOutDev& out, hipStream_t stream, int tier,
                            const uint32_t* items, uint32_t num_items, unsigned int* ctr,
                            uint32_t* grid_out);
+  // prepare_lhs once in.base_flags is set (from an rhs, or 0 without one)
+  hipError_t prepare_lhs_flags(LhsPrepIn in, hipStream_t stream, LhsPrepared* prepared);
   void* scratch(size_t idx, size_t bytes);
   int dev_;
   int num_cus_ = 0;

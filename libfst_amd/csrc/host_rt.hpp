@@ -240,6 +240,9 @@ FstError trim_lattices(DeviceEngine::Lease& E, const int32_t* status, LatShard& 
                        hipStream_t stream);
 // fst_connect_lhs_batch's shard: the items staged as run_lhs_shard stages them, then trimmed.
 FstError run_connect_shard(Shard& S, const FstLhsBatch& L);
+// fst_shortest_path_lhs_batch's shard: the items staged the same way, then fst_shortest_path of
+// each (DeviceEngine::run_sp_batch) into a path arena of the shard's states; S.keep = the paths.
+FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n);
 FstError run_pipelined(int dev, FrozenFst& b, const uint32_t* labels, const uint64_t* offsets,
                        uint32_t num, uint32_t n, int semantics, uint32_t parts,
                        FstBatchResult* out);

@@ -153,6 +153,9 @@ SIGNATURES = {
     "fst_device_compose_shortest_path_lhs": (
         C.c_int, [_u64, C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceBatch), _P]),
+    "fst_device_shortest_path_lhs": (
+        C.c_int, [C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstDeviceBatch), _P]),
     "fst_device_compose_shortest_path": (
         C.c_int, [_u64, _P, _P, _u32, _u32, _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceBatch), _P]),
@@ -166,6 +169,9 @@ SIGNATURES = {
     "fst_connect_lhs_batch": (
         C.c_int, [C.POINTER(FstLhsBatch), C.POINTER(FstBatchOptions),
                   C.POINTER(FstLatticeBatch)]),
+    "fst_shortest_path_lhs_batch": (
+        C.c_int, [C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstBatchResult)]),
     "fst_device_compose_frozen": (
         C.c_int, [_u64, _P, _P, _u32, _u32, _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceLattices), C.POINTER(_u64), _P]),
@@ -608,6 +614,21 @@ def connect_lhs_batch(lhs: LhsBatch, device: int = -1, devices=None,
     if rc != FST_OK:
         raise RuntimeError(f"fst_connect_lhs_batch failed: {rc}")
     return LatticeBatch(res)
+
+
+def shortest_path_lhs_batch(lhs: LhsBatch, n: int = 1, device: int = -1, devices=None,
+                            shards: int = 0) -> BatchResult:
+    """fst_shortest_path of every item of an lhs batch (fst_shortest_path_lhs_batch), with no
+    compose: per item what the single call returns, bit for bit, as a status and a 1-best
+    chain.  A non-OK item of a LatticeBatch owns no states and comes out EMPTY here: read the
+    producer's status first."""
+    opts = batch_options(device, FST_SEM_LAZY, devices, shards)
+    res = FstBatchResult()
+    cs = lhs.c_struct()
+    rc = lib().fst_shortest_path_lhs_batch(C.byref(cs), n, C.byref(opts), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_shortest_path_lhs_batch failed: {rc}")
+    return _take_result(res, len(lhs))
 
 
 def pipeline_lhs_batch(stages, lhs: LhsBatch, n: int = 1, semantics: int = FST_SEM_LAZY,
