@@ -170,26 +170,41 @@ bool lattice_flags_ok(uint32_t f) {
   return !(f & ~(FST_LATTICE_PROJECT_OUTPUT | FST_LATTICE_CONNECT));  // (bit 1 stays unknown)
 }
 
-// A checked batch of general lhs through `fs` (one stage: the lhs batch entry; several: stage
-// 1 on the lhs, then chain stages on the 1-best output tapes) into a label or a text result.
-// Shards are balanced by arcs + 1 per item.
+// run_sharded's costs of a batch of general lhs: arcs + 1 per item.
+std::vector<double> lhs_costs(const FstLhsBatch& lhs, uint32_t nsh) {
+  std::vector<double> cost(nsh > 1 ? lhs.num_fsts : 0);
+  for (size_t i = 0; i < cost.size(); ++i)
+    cost[i] = (double)(lhs.arc_offsets[lhs.state_offsets[i + 1]] -
+                       lhs.arc_offsets[lhs.state_offsets[i]]) + 1.0;
+  return cost;
+}
+
+// A checked batch of general lhs in shards balanced by lhs_costs: `shard` computes one (it gets
+// the call for its semantics) into a label, text or lattice result.  The empty batch is its OK
+// result before any GPU check.  `any_semantics`: the entry never looks at opts->semantics.
+template <class R, class F>
+FstError lhs_sharded(const FstLhsBatch* lhs, const FstBatchOptions* opts, bool any_semantics,
+                     R* out, const char* name, void (*release)(R*), const F& shard) {
+  if (lhs->num_fsts == 0) return empty_result(out);
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  if (!any_semantics && call.semantics != FST_SEM_LAZY && call.semantics != FST_SEM_EAGER)
+    return FST_INVALID_ARG;
+  const FstError e =
+      run_sharded(call.devices, call.nsh, lhs->num_fsts, lhs_costs(*lhs, call.nsh),
+                  [&](Shard& S) { return shard(S, call); }, out);
+  return call.close(e, name, out, release);
+}
+
+// ... through `fs` (one stage: the lhs batch entry; several: stage 1 on the lhs, then chain
+// stages on the 1-best output tapes).
 template <class R>
 FstError lhs_stages_impl(const Stages& fs, const FstLhsBatch* lhs, uint32_t n,
                          const FstBatchOptions* opts, R* out, const char* name,
                          void (*release)(R*)) {
-  const uint32_t num = lhs->num_fsts;
-  if (num == 0) return empty_result(out);
-  BatchCall call;
-  if (FstError e = call.open(opts); e != FST_OK) return e;
-  if (call.semantics != FST_SEM_LAZY && call.semantics != FST_SEM_EAGER) return FST_INVALID_ARG;
-  std::vector<double> cost(call.nsh > 1 ? num : 0);
-  for (size_t i = 0; i < cost.size(); ++i)
-    cost[i] = (double)(lhs->arc_offsets[lhs->state_offsets[i + 1]] -
-                       lhs->arc_offsets[lhs->state_offsets[i]]) + 1.0;
-  const FstError e = run_sharded(
-      call.devices, call.nsh, num, cost,
-      [&](Shard& S) { return run_lhs_pipeline_shard(S, fs, *lhs, n, call.semantics); }, out);
-  return call.close(e, name, out, release);
+  return lhs_sharded(lhs, opts, false, out, name, release, [&](Shard& S, const BatchCall& call) {
+    return run_lhs_pipeline_shard(S, fs, *lhs, n, call.semantics);
+  });
 }
 
 FstError lhs_batch_impl(FstHandle b_handle, const FstLhsBatch* lhs, uint32_t n,
@@ -200,15 +215,20 @@ FstError lhs_batch_impl(FstHandle b_handle, const FstLhsBatch* lhs, uint32_t n,
                          "fst_compose_frozen_shortest_path_lhs_batch", fst_batch_result_free);
 }
 
-// The argument checks of the two lhs pipeline entries (`out` checked and zeroed before): the
-// lhs batch entry's, plus the stages.
-bool lhs_pipeline_args(const FstHandle* stages, uint32_t num_stages, const FstLhsBatch* lhs,
-                       const FstBatchOptions* opts, Stages* fs) {
-  if (!stages || num_stages == 0 || !lhs_batch_valid(lhs) || !flags_ok(opts)) return false;
+// The stage handles of a pipeline entry, pinned; false: none, or a stale one.
+bool get_stages(const FstHandle* stages, uint32_t num_stages, Stages* fs) {
+  if (!stages || num_stages == 0) return false;
   fs->resize(num_stages);
   for (uint32_t k = 0; k < num_stages; ++k)
     if (!((*fs)[k] = frozen_get(stages[k]))) return false;
   return true;
+}
+
+// The argument checks of the two lhs pipeline entries (`out` checked and zeroed before): the
+// lhs batch entry's, plus the stages.
+bool lhs_pipeline_args(const FstHandle* stages, uint32_t num_stages, const FstLhsBatch* lhs,
+                       const FstBatchOptions* opts, Stages* fs) {
+  return lhs_batch_valid(lhs) && flags_ok(opts) && get_stages(stages, num_stages, fs);
 }
 
 // The prepare kernel's inputs for a device-resident lhs batch: the caller's device pointers and
@@ -233,6 +253,51 @@ FstError device_lhs_extents(const FstLhsBatch* d_lhs, hipStream_t s, LhsPrepIn* 
        (!d_lhs->ilabels || !d_lhs->olabels || !d_lhs->weights || !d_lhs->nextstates)))
     return FST_INVALID_ARG;
   return FST_OK;
+}
+
+// The frame of a device-side entry after its argument checks: the caller's device given back
+// when the entry returns, the device of `opts` (or the current one) made current, the rhs on it
+// (when there is one), an engine leased onto the caller's stream, and the drain: every return
+// waits for what the call queued, so the engine's workspaces are its own again.  The members
+// stand in the order the entries used to declare them; what the drain must outlive it
+// (fst_device_compose_frozen's arena) is declared before the frame.
+struct DeviceCall {
+  DeviceRestore_ restore;
+  int dev = -1;
+  DeviceFst* D = nullptr;
+  DeviceEngine::Lease E;
+  hipStream_t s = nullptr;
+  StreamDrain drain{{nullptr}, true};
+  FstError open(const FstBatchOptions* opts, FrozenFst* b, void* stream) {
+    if (!gpu_available()) return FST_INVALID_ARG;
+    dev = opts && opts->device >= 0 ? opts->device : current_device();
+    if (dev < 0 || hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+    if (b && !(D = b->device(dev))) return FST_OOM;
+    E = DeviceEngine::acquire(dev);
+    if (!E) return FST_INVALID_ARG;
+    drain.s[0] = s = E.use((hipStream_t)stream);
+    drain.done = false;
+    return FST_OK;
+  }
+};
+
+// The argument checks the two device-resident lhs entries share.
+bool device_lhs_args_ok(const FstLhsBatch* d_lhs) {
+  return d_lhs &&
+         (!d_lhs->num_fsts || (d_lhs->state_offsets && d_lhs->start && d_lhs->arc_offsets));
+}
+bool device_batch_out_ok(const FstDeviceBatch* o, uint32_t num) {
+  return o && o->arc_cursor &&
+         (!num || (o->status && o->path_len && o->path_offset && o->final_weight));
+}
+
+// ... and their preparation: the extents, then the prepare kernel (the rhs's flags with c.D).
+FstError device_lhs_prepare(DeviceCall& c, const FstLhsBatch* d_lhs, LhsBatchDev* batch,
+                            LhsPrepared* p) {
+  LhsPrepIn in{};
+  if (FstError e = device_lhs_extents(d_lhs, c.s, &in); e != FST_OK) return e;
+  return c.E->prepare_lhs(c.D, in, d_lhs->ilabels, c.s, batch, p) == hipSuccess ? FST_OK
+                                                                               : FST_OOM;
 }
 
 }  // namespace
@@ -407,18 +472,10 @@ FstError fst_compose_frozen_lhs_batch(FstHandle b_handle, const FstLhsBatch* lhs
     return FST_INVALID_ARG;
   std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
   if (!b) return FST_INVALID_ARG;
-  const uint32_t num = lhs->num_fsts;
-  if (num == 0) return empty_result(out);
-  BatchCall call;
-  if (FstError e = call.open(opts); e != FST_OK) return e;
-  std::vector<double> cost(call.nsh > 1 ? num : 0);
-  for (size_t i = 0; i < cost.size(); ++i)
-    cost[i] = (double)(lhs->arc_offsets[lhs->state_offsets[i + 1]] -
-                       lhs->arc_offsets[lhs->state_offsets[i]]) + 1.0;
-  const FstError e = run_sharded(
-      call.devices, call.nsh, num, cost,
-      [&](Shard& S) { return run_lattice_lhs_shard(S, *b, *lhs, lattice_flags); }, out);
-  return call.close(e, "fst_compose_frozen_lhs_batch", out, fst_lattice_batch_free);
+  return lhs_sharded(lhs, opts, true, out, "fst_compose_frozen_lhs_batch", fst_lattice_batch_free,
+                     [&](Shard& S, const BatchCall&) {
+                       return run_lattice_lhs_shard(S, *b, *lhs, lattice_flags);
+                     });
 }
 
 // Connect of every item of an lhs batch: no rhs, no engine ladder; the items are staged as the
@@ -428,18 +485,8 @@ FstError fst_connect_lhs_batch(const FstLhsBatch* lhs, const FstBatchOptions* op
   if (!out) return FST_INVALID_ARG;
   std::memset(out, 0, sizeof(*out));
   if (!lhs_batch_valid(lhs) || !flags_ok(opts)) return FST_INVALID_ARG;
-  const uint32_t num = lhs->num_fsts;
-  if (num == 0) return empty_result(out);
-  BatchCall call;
-  if (FstError e = call.open(opts); e != FST_OK) return e;
-  std::vector<double> cost(call.nsh > 1 ? num : 0);
-  for (size_t i = 0; i < cost.size(); ++i)
-    cost[i] = (double)(lhs->arc_offsets[lhs->state_offsets[i + 1]] -
-                       lhs->arc_offsets[lhs->state_offsets[i]]) + 1.0;
-  const FstError e = run_sharded(
-      call.devices, call.nsh, num, cost, [&](Shard& S) { return run_connect_shard(S, *lhs); },
-      out);
-  return call.close(e, "fst_connect_lhs_batch", out, fst_lattice_batch_free);
+  return lhs_sharded(lhs, opts, true, out, "fst_connect_lhs_batch", fst_lattice_batch_free,
+                     [&](Shard& S, const BatchCall&) { return run_connect_shard(S, *lhs); });
 }
 
 // fst_shortest_path of every item of an lhs batch: no rhs, no compose; the items are staged as
@@ -449,17 +496,8 @@ FstError fst_shortest_path_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
   if (!out) return FST_INVALID_ARG;
   std::memset(out, 0, sizeof(*out));
   if (!lhs_batch_valid(lhs) || !flags_ok(opts)) return FST_INVALID_ARG;
-  const uint32_t num = lhs->num_fsts;
-  if (num == 0) return empty_result(out);
-  BatchCall call;
-  if (FstError e = call.open(opts); e != FST_OK) return e;
-  std::vector<double> cost(call.nsh > 1 ? num : 0);
-  for (size_t i = 0; i < cost.size(); ++i)
-    cost[i] = (double)(lhs->arc_offsets[lhs->state_offsets[i + 1]] -
-                       lhs->arc_offsets[lhs->state_offsets[i]]) + 1.0;
-  const FstError e = run_sharded(
-      call.devices, call.nsh, num, cost, [&](Shard& S) { return run_sp_shard(S, *lhs, n); }, out);
-  return call.close(e, "fst_shortest_path_lhs_batch", out, fst_batch_result_free);
+  return lhs_sharded(lhs, opts, true, out, "fst_shortest_path_lhs_batch", fst_batch_result_free,
+                     [&](Shard& S, const BatchCall&) { return run_sp_shard(S, *lhs, n); });
 }
 
 void fst_lattice_batch_free(FstLatticeBatch* r) {
@@ -493,21 +531,15 @@ FstError fst_device_compose_frozen(FstHandle b_handle, const uint32_t* d_labels,
     return FST_INVALID_ARG;
   std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
   if (!b) return FST_INVALID_ARG;
-  if (!gpu_available()) return FST_INVALID_ARG;
-  DeviceRestore_ restore;
-  const int dev = opts && opts->device >= 0 ? opts->device : current_device();
-  if (dev < 0 || hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
-  DeviceFst* D = b->device(dev);
-  if (!D) return FST_OOM;
-  DeviceEngine::Lease E = DeviceEngine::acquire(dev);
-  if (!E) return FST_INVALID_ARG;
-  const hipStream_t s = E.use((hipStream_t)stream);
-  // the arena and the statuses are declared before the drain, so they are destroyed after
-  // it: every return waits for what the call queued (the gather reads the arena) before
-  // those blocks go back to the pool
+  // the arena and the statuses are declared before the drain (the frame's), so they are
+  // destroyed after it: every return waits for what the call queued (the gather reads the
+  // arena) before those blocks go back to the pool
   std::unique_ptr<LatShard> lat;
   std::unique_ptr<DevOut> keep;
-  StreamDrain drain{{s}};
+  DeviceCall call;
+  if (FstError e = call.open(opts, b.get(), stream); e != FST_OK) return e;
+  DeviceEngine::Lease& E = call.E;
+  const hipStream_t s = call.s;
   needed[0] = needed[1] = 0;
   ChainInput in{{d_labels}, d_offsets, num_strings, max_len};
   uint64_t first = 0, last = 0;
@@ -515,28 +547,19 @@ FstError fst_device_compose_frozen(FstHandle b_handle, const uint32_t* d_labels,
     return FST_OOM;
   if (last < first) return FST_INVALID_ARG;
   const uint64_t est = 8 * ((last - first) + num_strings) + 4ull * num_strings + 1024;
-  if (FstError e = run_lattice_arena(E, *D, in, nullptr, lattice_flags, est, 2 * est, &lat, &keep);
+  if (FstError e = run_lattice_arena(E, *call.D, in, nullptr, lattice_flags, est, 2 * est, &lat, &keep);
       e != FST_OK)
     return e;
-  LatticeCsrDev csr{};
-  csr.status = o->status;
-  csr.state_offsets = o->state_offsets;
-  csr.start = o->start;
-  csr.final_w = o->final_weights;
-  csr.arc_offsets = o->arc_offsets;
-  csr.il = o->ilabels;
-  csr.ol = o->olabels;
-  csr.w = o->weights;
-  csr.next = o->nextstates;
-  csr.state_cap = o->state_capacity;
-  csr.arc_cap = o->arc_capacity;
-  if (E->compact_lattices_count(keep->v.status, lat->arena, num_strings, csr, needed, s) !=
-      hipSuccess)
+  const LatticeCsrDev csr{o->status,      o->state_offsets, o->start,   o->final_weights,
+                          o->arc_offsets, o->ilabels,       o->olabels, o->weights,
+                          o->nextstates,  o->state_capacity, o->arc_capacity};
+  const LatticeOutDev& arena = lat->arena.v;
+  if (E->compact_lattices_count(keep->v.status, arena, num_strings, csr, needed, s) != hipSuccess)
     return FST_OOM;
-  if (needed[0] > lat->arena.state_cap || needed[1] > lat->arena.arc_cap) return FST_OOM;
+  if (needed[0] > arena.state_cap || needed[1] > arena.arc_cap) return FST_OOM;
   // too small: the statuses and `needed` stand, nothing else is written
   if (needed[0] > csr.state_cap || needed[1] > csr.arc_cap) return FST_OK;
-  if (E->compact_lattices(lat->arena, num_strings, csr, s, lat->connect ? &lat->trim : nullptr) !=
+  if (E->compact_lattices(arena, num_strings, csr, s, lat->connect ? &lat->trim.v : nullptr) !=
       hipSuccess)
     return FST_OOM;
   return FST_OK;  // (the drain waits for the gather, then `keep` and `lat` go)
@@ -549,54 +572,28 @@ FstError fst_device_compose_frozen(FstHandle b_handle, const uint32_t* d_labels,
 FstError fst_device_compose_shortest_path_lhs(FstHandle b_handle, const FstLhsBatch* d_lhs,
                                               uint32_t n, const FstBatchOptions* opts,
                                               const FstDeviceBatch* o, void* stream) {
-  if (!o || !d_lhs || !flags_ok(opts)) return FST_INVALID_ARG;
-  const uint32_t num = d_lhs->num_fsts;
-  if (num && (!d_lhs->state_offsets || !d_lhs->start || !d_lhs->arc_offsets))
-    return FST_INVALID_ARG;
-  if (!o->arc_cursor || (num && (!o->status || !o->path_len || !o->path_offset || !o->final_weight)))
+  if (!device_lhs_args_ok(d_lhs) || !device_batch_out_ok(o, d_lhs->num_fsts) || !flags_ok(opts))
     return FST_INVALID_ARG;
   const int semantics = opts ? (int)opts->semantics : FST_SEM_LAZY;
   if (semantics != FST_SEM_LAZY && semantics != FST_SEM_EAGER) return FST_INVALID_ARG;
   std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
   if (!b) return FST_INVALID_ARG;
-  if (!gpu_available()) return FST_INVALID_ARG;
-  DeviceRestore_ restore;
-  const int dev = opts && opts->device >= 0 ? opts->device : current_device();
-  if (dev < 0 || hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
-  DeviceFst* D = b->device(dev);
-  if (!D) return FST_OOM;
-  DeviceEngine::Lease E = DeviceEngine::acquire(dev);
-  if (!E) return FST_INVALID_ARG;
-  const hipStream_t s = E.use((hipStream_t)stream);
-  // every return waits for what the call queued: the engine's workspaces are its own again
-  StreamDrain drain{{s}};
-  LhsPrepIn in{};
-  if (FstError e = device_lhs_extents(d_lhs, s, &in); e != FST_OK) return e;
+  DeviceCall call;
+  if (FstError e = call.open(opts, b.get(), stream); e != FST_OK) return e;
+  LhsBatchDev batch;
   LhsPrepared p;
-  if (E->prepare_lhs(*D, in, s, &p) != hipSuccess) return FST_OOM;
-  if (p.max_outdeg >= (1u << 30)) return FST_OOM;  // the lazy per-pop table is 2 * deg + 2 entries
-  ChainInput ci{};
-  ci.lhs_desc = p.desc;
-  ci.num_strings = num;
-  GraphInput g{};
-  g.state_off = p.state_off;
-  g.final_w = d_lhs->final_weights;
-  g.arc_w = d_lhs->weights;
-  g.arc_il = d_lhs->ilabels;
-  g.arc_ol = d_lhs->olabels;
-  g.arc_next = d_lhs->nextstates;
-  g.start = kNoState;
-  g.max_outdeg = p.max_outdeg;
+  if (FstError e = device_lhs_prepare(call, d_lhs, &batch, &p); e != FST_OK) return e;
+  // the lazy per-pop table is 2 * deg + 2 entries
+  if (batch.lhs.max_outdeg >= (1u << 30)) return FST_OOM;
   LaunchStats st;
-  LhsRoute route;
-  if (E->run_lhs_batch(*D, ci, g, n, semantics, p.items_nonneg, p.num_nonneg, p.items_replay,
-                       p.num_replay, dev_out(o), s, &st, &route) != hipSuccess)
+  if (call.E->run_lhs_batch(*call.D, batch, n, semantics, dev_out(o), call.s, &st, nullptr) !=
+      hipSuccess)
     return FST_OOM;
   st.launches += p.launches;
   t_last_stats = st;
   // (run_lhs_batch waited for its last tier: with stats it ends on an event of the stream;
   // an empty batch queued one memset, which the drain still waits for)
-  drain.done = num != 0;
+  call.drain.done = d_lhs->num_fsts != 0;
   return FST_OK;
 }
 
@@ -605,45 +602,19 @@ FstError fst_device_compose_shortest_path_lhs(FstHandle b_handle, const FstLhsBa
 FstError fst_device_shortest_path_lhs(const FstLhsBatch* d_lhs, uint32_t n,
                                       const FstBatchOptions* opts, const FstDeviceBatch* o,
                                       void* stream) {
-  if (!o || !d_lhs || !flags_ok(opts)) return FST_INVALID_ARG;
-  const uint32_t num = d_lhs->num_fsts;
-  if (num && (!d_lhs->state_offsets || !d_lhs->start || !d_lhs->arc_offsets))
+  if (!device_lhs_args_ok(d_lhs) || !device_batch_out_ok(o, d_lhs->num_fsts) || !flags_ok(opts))
     return FST_INVALID_ARG;
-  if (!o->arc_cursor || (num && (!o->status || !o->path_len || !o->path_offset || !o->final_weight)))
-    return FST_INVALID_ARG;
-  if (!gpu_available()) return FST_INVALID_ARG;
-  DeviceRestore_ restore;
-  const int dev = opts && opts->device >= 0 ? opts->device : current_device();
-  if (dev < 0 || hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
-  DeviceEngine::Lease E = DeviceEngine::acquire(dev);
-  if (!E) return FST_INVALID_ARG;
-  const hipStream_t s = E.use((hipStream_t)stream);
-  // every return waits for what the call queued: the engine's workspaces are its own again
-  StreamDrain drain{{s}};
-  LhsPrepIn in{};
-  if (FstError e = device_lhs_extents(d_lhs, s, &in); e != FST_OK) return e;
+  DeviceCall call;
+  if (FstError e = call.open(opts, nullptr, stream); e != FST_OK) return e;
+  LhsBatchDev batch;
   LhsPrepared p;
-  if (E->prepare_lhs(in, s, &p) != hipSuccess) return FST_OOM;
-  ChainInput ci{};
-  ci.lhs_desc = p.desc;
-  ci.num_strings = num;
-  GraphInput g{};
-  g.state_off = p.state_off;
-  g.final_w = d_lhs->final_weights;
-  g.arc_w = d_lhs->weights;
-  g.arc_il = d_lhs->ilabels;
-  g.arc_ol = d_lhs->olabels;
-  g.arc_next = d_lhs->nextstates;
-  g.start = kNoState;
-  g.max_outdeg = p.max_outdeg;
+  if (FstError e = device_lhs_prepare(call, d_lhs, &batch, &p); e != FST_OK) return e;
   LaunchStats st;
-  LhsRoute route;
-  if (E->run_sp_batch(ci, g, in.total_states, in.total_arcs, n, p.items_nonneg, p.num_nonneg,
-                      p.items_replay, p.num_replay, dev_out(o), s, &st, &route) != hipSuccess)
+  if (call.E->run_sp_batch(batch, n, dev_out(o), call.s, &st, nullptr) != hipSuccess)
     return FST_OOM;
   st.launches += p.launches;
   t_last_stats = st;
-  drain.done = true;  // (run_sp_batch synchronised the stream)
+  call.drain.done = true;  // (run_sp_batch synchronised the stream)
   return FST_OK;
 }
 
@@ -671,9 +642,8 @@ FstError fst_pipeline_batch(const FstHandle* stages, uint32_t num_stages, const 
     return FST_INVALID_ARG;
   std::memset(out, 0, sizeof(*out));
   if (!offsets_monotone(offsets, num_strings) || !flags_ok(opts)) return FST_INVALID_ARG;
-  Stages fs(num_stages);
-  for (uint32_t k = 0; k < num_stages; ++k)
-    if (!(fs[k] = frozen_get(stages[k]))) return FST_INVALID_ARG;
+  Stages fs;
+  if (!get_stages(stages, num_stages, &fs)) return FST_INVALID_ARG;
   BatchCall call;
   if (FstError e = call.open(opts); e != FST_OK) return e;
   const FstError e = run_sharded(
@@ -696,17 +666,9 @@ FstError fst_normalize_text_batch(const FstHandle* stages, uint32_t num_stages,
     return FST_INVALID_ARG;
   std::memset(out, 0, sizeof(*out));
   if (!offsets_monotone(offsets, num_strings) || !flags_ok(opts)) return FST_INVALID_ARG;
-  Stages fs(num_stages);
-  for (uint32_t k = 0; k < num_stages; ++k)
-    if (!(fs[k] = frozen_get(stages[k]))) return FST_INVALID_ARG;
-  if (num_strings == 0) {  // nothing to run: the empty result
-    if (!alloc_text_result(out, 0, 0)) {
-      fst_text_result_free(out);
-      return FST_OOM;
-    }
-    out->text_offsets[0] = 0;
-    return FST_OK;
-  }
+  Stages fs;
+  if (!get_stages(stages, num_stages, &fs)) return FST_INVALID_ARG;
+  if (num_strings == 0) return empty_result(out);  // nothing to run
   BatchCall call;
   if (FstError e = call.open(opts); e != FST_OK) return e;
   const int semantics = call.semantics;
@@ -820,6 +782,7 @@ FstError fst_device_compose_shortest_path(FstHandle b_handle, const uint32_t* d_
                                           uint32_t max_len, uint32_t n,
                                           const FstBatchOptions* opts, const FstDeviceBatch* o,
                                           void* stream) {
+  // (outside DeviceCall: no device restore, no flags_ok check and no drain, as it always was)
   if (!o || !d_offsets) return FST_INVALID_ARG;
   std::shared_ptr<FrozenFst> b = frozen_get(b_handle);
   if (!b) return FST_INVALID_ARG;
@@ -828,7 +791,7 @@ FstError fst_device_compose_shortest_path(FstHandle b_handle, const uint32_t* d_
   if (dev < 0 || hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
   DeviceFst* D = b->device(dev);
   if (!D) return FST_OOM;
-  ChainInput in{d_labels, d_offsets, num_strings, max_len};
+  ChainInput in{{d_labels}, d_offsets, num_strings, max_len};
   DeviceEngine::Lease E = DeviceEngine::acquire(dev);
   if (!E) return FST_INVALID_ARG;
   const hipStream_t s = E.use((hipStream_t)stream);

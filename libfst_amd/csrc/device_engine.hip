@@ -2824,14 +2824,13 @@ hipError_t DeviceEngine::run_lhs_eager(const DeviceFst& rhs, const ChainInput& i
   return run_bfs_ladder(count, list, list2, cnt, out.status, L, stream, route, grid_out);
 }
 
-hipError_t DeviceEngine::run_lhs_batch(const DeviceFst& rhs, const ChainInput& in,
-                                       const GraphInput& lhs, uint32_t n, int semantics,
-                                       const uint32_t* items_nonneg, uint32_t num_nonneg,
-                                       const uint32_t* items_replay, uint32_t num_replay,
-                                       const BatchOutDev& out, hipStream_t stream,
+hipError_t DeviceEngine::run_lhs_batch(const DeviceFst& rhs, const LhsBatchDev& b, uint32_t n,
+                                       int semantics, const BatchOutDev& out, hipStream_t stream,
                                        LaunchStats* stats, LhsRoute* route) {
   HIP_TRY(hipSetDevice(dev_));
   if (semantics != 0 && semantics != 1) return hipErrorInvalidValue;
+  const ChainInput& in = b.in;
+  const GraphInput& lhs = b.lhs;
   const uint32_t num = in.num_strings;
   unsigned int* counter = (unsigned int*)scratch(kCounter, kCounterBytes);
   if (!counter) return hipErrorOutOfMemory;
@@ -2845,10 +2844,10 @@ hipError_t DeviceEngine::run_lhs_batch(const DeviceFst& rhs, const ChainInput& i
   if (stats) stats->engine = semantics == 0 ? 8 : 9;  // (7 is the lazy pull tier)
   HIP_TRY(timed(stats, stream, [&]() -> hipError_t {
     if (semantics == 1) {
-      r.replay = num_replay;
-      HIP_TRY(run_lhs_eager(rhs, in, lhs, n, items_nonneg, num_nonneg, false, out, stream, &r,
-                            &grid));
-      return run_lhs_eager(rhs, in, lhs, n, items_replay, num_replay, true, out, stream, &r,
+      r.replay = b.num_replay;
+      HIP_TRY(run_lhs_eager(rhs, in, lhs, n, b.items_nonneg, b.num_nonneg, false, out, stream,
+                            &r, &grid));
+      return run_lhs_eager(rhs, in, lhs, n, b.items_replay, b.num_replay, true, out, stream, &r,
                            &grid);
     }
     // table tiers of 1024 tuples x16 up to the single call's 2^26, each over the list of the
@@ -3007,14 +3006,11 @@ hipError_t DeviceEngine::compact_lattices(const LatticeOutDev& lat, uint32_t num
 
 // ---- lattice shortest path (lattice_sp.hip holds the kernels) ---------------------------
 
-hipError_t DeviceEngine::run_sp_batch(const ChainInput& in, const GraphInput& lhs,
-                                      uint64_t total_states, uint64_t total_arcs, uint32_t n,
-                                      const uint32_t* items_nonneg, uint32_t num_nonneg,
-                                      const uint32_t* items_replay, uint32_t num_replay,
-                                      const BatchOutDev& out, hipStream_t stream,
-                                      LaunchStats* stats, LhsRoute* route) {
+hipError_t DeviceEngine::run_sp_batch(const LhsBatchDev& b, uint32_t n, const BatchOutDev& out,
+                                      hipStream_t stream, LaunchStats* stats, LhsRoute* route) {
   HIP_TRY(hipSetDevice(dev_));
-  const uint32_t num = in.num_strings;
+  const GraphInput& lhs = b.lhs;
+  const uint32_t num = b.in.num_strings, num_nonneg = b.num_nonneg, num_replay = b.num_replay;
   HIP_TRY(hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), stream));
   if (stats) {
     stats->engine = 12;
@@ -3028,9 +3024,9 @@ hipError_t DeviceEngine::run_sp_batch(const ChainInput& in, const GraphInput& lh
     if (*e) sweeps = (uint32_t)std::min<unsigned long long>(std::strtoull(e, nullptr, 10), 1u << 20);
   const uint32_t cap = grid_cap("FSTAMD_GRAPH_GRID");
   const uint32_t cus = (uint32_t)std::max(num_cus_, 1);
-  const size_t sw = ((size_t)total_states + 4) * 4;
+  const size_t sw = ((size_t)b.total_states + 4) * 4;
   LatSpDev p{};
-  p.desc = in.lhs_desc;
+  p.desc = b.in.lhs_desc;
   p.state_off = lhs.state_off;
   p.final_w = lhs.final_w;
   p.arc_next = lhs.arc_next;
@@ -3043,8 +3039,8 @@ hipError_t DeviceEngine::run_sp_batch(const ChainInput& in, const GraphInput& lh
   p.ctr = (uint32_t*)scratch(kSpCtr, kSpCtrWords * 4);
   if (!p.key || !p.back || !p.list || !p.ctr) return hipErrorOutOfMemory;
   if (num_replay) {
-    p.heap = (SpHeapEnt*)scratch(kSpHeap, ((size_t)total_arcs + num) * 16);
-    p.settled = (uint8_t*)scratch(kSpSettled, (size_t)total_states + 16);
+    p.heap = (SpHeapEnt*)scratch(kSpHeap, ((size_t)b.total_arcs + num) * 16);
+    p.settled = (uint8_t*)scratch(kSpSettled, (size_t)b.total_states + 16);
     if (!p.heap || !p.settled) return hipErrorOutOfMemory;
   }
   p.sweeps = sweeps;
@@ -3058,13 +3054,13 @@ hipError_t DeviceEngine::run_sp_batch(const ChainInput& in, const GraphInput& lh
   HIP_TRY(timed(stats, stream, [&]() -> hipError_t {
     if (num_nonneg) {
       const uint32_t g = std::max<uint32_t>(1, std::min({num_nonneg, cus * 32, cap}));
-      HIP_TRY(launch_sp_wave(p, items_nonneg, num_nonneg, out, g, stream));
+      HIP_TRY(launch_sp_wave(p, b.items_nonneg, num_nonneg, out, g, stream));
       grid_max = std::max(grid_max, g);
       ++launches;
     }
     if (num_replay) {
       const uint32_t g = std::max<uint32_t>(1, std::min({num_replay, cus * 32, cap}));
-      HIP_TRY(launch_sp_replay(p, items_replay, num_replay, out, g, stream));
+      HIP_TRY(launch_sp_replay(p, b.items_replay, num_replay, out, g, stream));
       grid_max = std::max(grid_max, g);
       ++launches;
     }
@@ -3104,22 +3100,23 @@ hipError_t DeviceEngine::run_sp_batch(const ChainInput& in, const GraphInput& lh
   return hipSuccess;
 }
 
-hipError_t DeviceEngine::prepare_lhs(const DeviceFst& rhs, LhsPrepIn in, hipStream_t stream,
+hipError_t DeviceEngine::prepare_lhs(const DeviceFst* rhs, LhsPrepIn in, const uint32_t* arc_il,
+                                     hipStream_t stream, LhsBatchDev* batch,
                                      LhsPrepared* prepared) {
-  in.base_flags = (rhs.nan ? kLhsNaN : 0u) | (rhs.nonneg ? 0u : kLhsReplay);
-  return prepare_lhs_flags(in, stream, prepared);
-}
-
-hipError_t DeviceEngine::prepare_lhs(LhsPrepIn in, hipStream_t stream, LhsPrepared* prepared) {
-  in.base_flags = 0;
-  return prepare_lhs_flags(in, stream, prepared);
-}
-
-hipError_t DeviceEngine::prepare_lhs_flags(LhsPrepIn in, hipStream_t stream,
-                                           LhsPrepared* prepared) {
+  in.base_flags = lhs_base_flags(rhs);
   HIP_TRY(hipSetDevice(dev_));
   *prepared = LhsPrepared();
+  *batch = LhsBatchDev();
   const uint32_t num = in.num;
+  batch->in.num_strings = num;
+  batch->lhs.final_w = in.final_w;
+  batch->lhs.arc_w = in.arc_w;
+  batch->lhs.arc_il = arc_il;
+  batch->lhs.arc_ol = in.arc_ol;
+  batch->lhs.arc_next = in.arc_next;
+  batch->lhs.start = kNoState;
+  batch->total_states = in.total_states;
+  batch->total_arcs = in.total_arcs;
   if (num == 0) return hipStreamSynchronize(stream);
   LhsPrepOut out{};
   out.desc = (LhsDesc*)scratch(kLhsPrepDesc, (size_t)num * sizeof(LhsDesc));
@@ -3148,13 +3145,13 @@ hipError_t DeviceEngine::prepare_lhs_flags(LhsPrepIn in, hipStream_t stream,
   }
   if ((uint64_t)totals[0] + totals[1] != num) return hipErrorUnknown;  // (the lists' invariant)
   if (totals[4] != 0 && totals[3] != num) return hipErrorUnknown;      // (the second pass's)
-  prepared->desc = out.desc;
-  prepared->state_off = out.state_off;
-  prepared->items_nonneg = nonneg;
-  prepared->items_replay = replay;
-  prepared->num_nonneg = totals[0];
-  prepared->num_replay = totals[1];
-  prepared->max_outdeg = totals[2];
+  batch->in.lhs_desc = out.desc;
+  batch->lhs.state_off = out.state_off;
+  batch->lhs.max_outdeg = totals[2];
+  batch->items_nonneg = nonneg;
+  batch->items_replay = replay;
+  batch->num_nonneg = totals[0];
+  batch->num_replay = totals[1];
   prepared->invalid = totals[3];
   if (std::getenv("FSTAMD_ROUTE_LOG"))
     std::fprintf(stderr,

@@ -565,15 +565,28 @@ hipError_t launch_lhs_prepare(const LhsPrepIn& in, const LhsPrepOut& out, uint32
                               hipStream_t stream);
 hipError_t launch_lhs_lists(const LhsDesc* desc, uint32_t num, uint32_t* list_nonneg,
                             uint32_t* list_replay, uint32_t* totals, hipStream_t stream);
-// What DeviceEngine::prepare_lhs leaves in the engine's workspaces for run_lhs_batch.
+// A batch of general lhs in device memory, as run_lhs_batch, run_sp_batch and the lattice batch
+// read it.  Both routes end up with one: the host route stages the caller's items into a block
+// of its own (host::stage_lhs_items), the device-resident route derives it from the caller's
+// arrays in place (DeviceEngine::prepare_lhs).
+struct LhsBatchDev {
+  ChainInput in{};    // lhs_desc = the items' descriptors, num_strings = their number
+  GraphInput lhs{};   // the whole batch's concatenated CSR (start / num_states unused,
+                      // max_outdeg = the batch's)
+  const uint32_t* items_nonneg = nullptr;  // device lists of the items without / with
+  const uint32_t* items_replay = nullptr;  // LhsDesc::flags & kLhsReplay ...
+  uint32_t num_nonneg = 0, num_replay = 0;  // ... and their host counts
+  uint64_t total_states = 0, total_arcs = 0;  // the batch's extents
+};
+// What else DeviceEngine::prepare_lhs reports.
 struct LhsPrepared {
-  const LhsDesc* desc = nullptr;
-  const uint32_t* state_off = nullptr;
-  const uint32_t* items_nonneg = nullptr;
-  const uint32_t* items_replay = nullptr;
-  uint32_t num_nonneg = 0, num_replay = 0, max_outdeg = 0, invalid = 0;
+  uint32_t invalid = 0;   // items that failed validation
   uint32_t launches = 0;
 };
+// The rhs's share of every item's flags (no rhs: none; an item's flags are then its own).
+inline uint32_t lhs_base_flags(const DeviceFst* rhs) {
+  return rhs ? (rhs->nan ? kLhsNaN : 0u) | (rhs->nonneg ? 0u : kLhsReplay) : 0u;
+}
 
 // What a batch of general lhs took which way (FSTAMD_ROUTE_LOG, tests): items that entered
 // each tier.  Eager: t[0..3] = tiny128, tiny256, tier 0, tiers 1+ (summed); replay = items on
@@ -665,42 +678,32 @@ class DeviceEngine {
   static void trim_idle(int dev, const DeviceEngine* except = nullptr);
   hipError_t run_graph(const DeviceFst& rhs, const GraphInput& in, uint32_t n, int semantics,
                        const BatchOutDev& out, hipStream_t stream, LaunchStats* stats);
-  // A batch of general lhs (fst_compose_frozen_shortest_path_lhs_batch): `lhs` holds the
-  // whole batch's concatenated CSR (start / num_states unused, max_outdeg = the batch's),
-  // in.lhs_desc the items' descriptors, in.num_strings their number.  Lazy (semantics 0):
-  // the hashed replay, one wave per item, table tiers 1024 tuples x16 up to 2^26.  Eager (1):
-  // the general BFS engine's tier ladder with the 1-best in the kernel; items_nonneg /
-  // items_replay (device lists, with their host counts) split the items by
-  // LhsDesc::flags & kLhsReplay.  Items no tier holds end OVERFLOW.  Synchronises on `stream`
-  // between tiers.
-  hipError_t run_lhs_batch(const DeviceFst& rhs, const ChainInput& in, const GraphInput& lhs,
-                           uint32_t n, int semantics, const uint32_t* items_nonneg,
-                           uint32_t num_nonneg, const uint32_t* items_replay,
-                           uint32_t num_replay, const BatchOutDev& out, hipStream_t stream,
-                           LaunchStats* stats, LhsRoute* route);
-  // The inputs of run_lhs_batch for a batch that is already in device memory
-  // (fst_device_compose_shortest_path_lhs): lhs_prepare_kernel validates every item against
-  // in.total_states / total_arcs and writes descriptors, local arc offsets and flags into the
-  // engine's workspaces (kinds of their own: run_lhs_batch uses the others in the same call);
-  // lhs_lists_kernel builds the two eager item lists; one small D2H brings the totals back.
-  // A batch whose state_offsets decrease somewhere is prepared a second time with every item
-  // invalid.  Synchronises `stream`.  in.base_flags is set here from the rhs.
-  hipError_t prepare_lhs(const DeviceFst& rhs, LhsPrepIn in, hipStream_t stream,
-                         LhsPrepared* prepared);
-  // The same with no rhs (fst_device_shortest_path_lhs): in.base_flags is 0, so an item's flags
-  // are the item's own.
-  hipError_t prepare_lhs(LhsPrepIn in, hipStream_t stream, LhsPrepared* prepared);
+  // A batch of general lhs (fst_compose_frozen_shortest_path_lhs_batch), `b` as LhsBatchDev
+  // describes it.  Lazy (semantics 0): the hashed replay, one wave per item, table tiers 1024
+  // tuples x16 up to 2^26.  Eager (1): the general BFS engine's tier ladder with the 1-best in
+  // the kernel, over b's two item lists in turn.  Items no tier holds end OVERFLOW.
+  // Synchronises on `stream` between tiers.
+  hipError_t run_lhs_batch(const DeviceFst& rhs, const LhsBatchDev& b, uint32_t n, int semantics,
+                           const BatchOutDev& out, hipStream_t stream, LaunchStats* stats,
+                           LhsRoute* route);
+  // The LhsBatchDev of a batch that is already in device memory (the device-resident lhs
+  // entries): lhs_prepare_kernel validates every item against in.total_states / total_arcs and
+  // writes descriptors, local arc offsets and flags into the engine's workspaces (kinds of
+  // their own: run_lhs_batch uses the others in the same call); lhs_lists_kernel builds the two
+  // eager item lists; one small D2H brings the totals back.  The batch's arc arrays are the
+  // caller's, read in place (`arc_il`: the one the prepare kernel does not read).  A batch whose
+  // state_offsets decrease somewhere is prepared a second time with every item invalid.
+  // in.base_flags is set here, from the rhs (lhs_base_flags; null: no rhs,
+  // fst_device_shortest_path_lhs).  Synchronises `stream`.
+  hipError_t prepare_lhs(const DeviceFst* rhs, LhsPrepIn in, const uint32_t* arc_il,
+                         hipStream_t stream, LhsBatchDev* batch, LhsPrepared* prepared);
   // fst_shortest_path of every item of an lhs batch (fst_shortest_path_lhs_batch; kernels/
-  // lattice_sp.hpp): in / lhs / the two item lists as for run_lhs_batch, total_states /
-  // total_arcs the batch's extents (they size the workspaces).  The wave tier takes the
-  // non-negative items and hands what its sweep budget (FSTAMD_SP_SWEEPS) does not settle to the
-  // frontier tier; the replay tier takes the others.  Items the arena cannot hold end
-  // OUTPUT_FULL, the cursor at what the batch needs.  Synchronises `stream`.
-  hipError_t run_sp_batch(const ChainInput& in, const GraphInput& lhs, uint64_t total_states,
-                          uint64_t total_arcs, uint32_t n, const uint32_t* items_nonneg,
-                          uint32_t num_nonneg, const uint32_t* items_replay,
-                          uint32_t num_replay, const BatchOutDev& out, hipStream_t stream,
-                          LaunchStats* stats, LhsRoute* route);
+  // lattice_sp.hpp); b's extents size the workspaces.  The wave tier takes the non-negative
+  // items and hands what its sweep budget (FSTAMD_SP_SWEEPS) does not settle to the frontier
+  // tier; the replay tier takes the others.  Items the arena cannot hold end OUTPUT_FULL, the
+  // cursor at what the batch needs.  Synchronises `stream`.
+  hipError_t run_sp_batch(const LhsBatchDev& b, uint32_t n, const BatchOutDev& out,
+                          hipStream_t stream, LaunchStats* stats, LhsRoute* route);
   // fst_compose_frozen: the whole lattice of one general lhs (kernels/eager_bfs.hpp), on
   // `stream` (synchronised: the lattice is downloaded).
   hipError_t compose_lattice(const DeviceFst& rhs, const GraphInput& lhs, HostLattice* lat,
@@ -866,8 +869,6 @@ class DeviceEngine {
                            const BatchOutDev& out, hipStream_t stream, int tier,
                            const uint32_t* items, uint32_t num_items, unsigned int* ctr,
                            uint32_t* grid_out);
-  // prepare_lhs once in.base_flags is set (from an rhs, or 0 without one)
-  hipError_t prepare_lhs_flags(LhsPrepIn in, hipStream_t stream, LhsPrepared* prepared);
   void* scratch(size_t idx, size_t bytes);
   int dev_;
   int num_cus_ = 0;

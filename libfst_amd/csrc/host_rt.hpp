@@ -1,7 +1,8 @@
 // host_rt.hpp -- what the host units of the C ABI share (internal, not installed): the
 // pooled buffers, the per-call profile, the shard types and the batch routes' signatures.
 // c_api.cpp holds the handle tables and the single calls, host_rt.cpp the pools and small
-// helpers, batch_sharded.cpp / batch_streamed.cpp the routes, batch_entries.cpp fst_batch.h.
+// helpers, batch_sharded.cpp (chains through the path arena), batch_lhs.cpp (general lhs and the
+// lattice batch) and batch_streamed.cpp the routes, batch_entries.cpp fst_batch.h.
 // stream_plan.hpp (included here, no HIP in it) holds what those routes decide and hand over on
 // the host alone: the streamed batch's knobs (StreamKnobs), its part and shard cuts, the label
 // route's compaction, and the gates and thread groups (PartGate, RecordedGate, ThreadGroup)
@@ -149,18 +150,35 @@ struct HostProf {
 // lease (its device outputs kept), compacted to CSR on the device (count, scan, gather:
 // DeviceEngine::compact_paths), then downloaded straight into the caller's result at the
 // shard's string and arc offsets.
-// A lattice shard (fst_compose_frozen_batch): the arena the emitting kernels filled, then --
-// after the sink's compaction -- the shard in FstLhsBatch's layout on the device.
+// A lattice shard (fst_compose_frozen_batch, fst_connect_lhs_batch; batch_lhs.cpp): the arena
+// the emitting kernels filled, the trim's workspace, and -- after the sink's compaction -- the
+// shard in FstLhsBatch's layout on the device.
+// Release order: shard_lattice_compact releases `trim` and `arena` once its gather has been
+// waited for; `csr` lives until the shard's download has.  Each `v` is the kernels' view of the
+// buffers beside it.  Whoever queues work on them declares its StreamDrain after the LatShard.
 struct LatShard {
-  std::unique_ptr<DevBuf> item, afin, aaoff, ail, aol, aw, anext, cursor;  // the arena
-  LatticeOutDev arena{};
-  std::unique_ptr<DevBuf> status, soff, start, fin, aoffs, il, ol, w, next;  // compacted
+  struct Arena {
+    std::unique_ptr<DevBuf> item, fin, aoff, il, ol, w, next, cursor;
+    // fst_connect_lhs_batch: `v` points into the staged items (run_connect_shard), kept here
+    std::shared_ptr<void> input;
+    LatticeOutDev v{};
+    // `num` items, the capacities multiples of 4; false: out of memory
+    bool alloc(uint32_t num, uint64_t state_cap, uint64_t arc_cap);
+    void release() { *this = Arena(); }
+  } arena;
   // FST_LATTICE_CONNECT / fst_connect_lhs_batch: the trim's workspace (trim_lattices), alive
-  // until the filtering gather has run; `input`: the staged items a stand-alone arena points into
+  // until the filtering gather has run
+  struct Trim {
+    std::unique_ptr<DevBuf> mark, queue, roff, rcur, rsrc, list, ctr, start;
+    LatTrimDev v{};
+    void release() { *this = Trim(); }
+  } trim;
   bool connect = false;
-  std::unique_ptr<DevBuf> tmark, tqueue, troff, trcur, trsrc, tlist, tctr, tstart;
-  LatTrimDev trim{};
-  std::shared_ptr<void> input;
+  struct Csr {  // the compacted shard
+    std::unique_ptr<DevBuf> status, soff, start, fin, aoffs, il, ol, w, next;
+    // the arrays there are so far (the counting step has the per-item ones alone)
+    LatticeCsrDev view(uint64_t state_cap, uint64_t arc_cap) const;
+  } csr;
 };
 
 struct Shard {
@@ -191,12 +209,32 @@ struct ShardSink {
 };
 using ShardCompute = std::function<FstError(Shard&)>;
 
-// ---- batch_sharded.cpp ----
+// ---- batch_sharded.cpp: chains through the path arena ----
+// One engine run into a path arena of `arc_cap` slots, rerun with a larger arena while a
+// string is OUTPUT_FULL.  `launch` queues the engine on `stream`; `failed` names it in the
+// error message.  With `keep` the device outputs stay alive and `h` receives only the
+// statuses; without it `h` receives everything.  `fine_laps`: the chain route's profile
+// also times the arena allocation and the download on their own.
+using ArenaLaunch = std::function<hipError_t(const BatchOutDev&, LaunchStats*)>;
+FstError run_arena(hipStream_t stream, uint32_t num, uint64_t arc_cap, const char* failed,
+                   bool fine_laps, const ArenaLaunch& launch, HostPaths* h,
+                   std::unique_ptr<DevOut>* keep);
 // One batch on device inputs; the path arena grows on OUTPUT_FULL.  With `keep` the
 // device outputs stay alive (pipelines) and `h` receives only the statuses.
 FstError run_chain_batch_dev(DeviceEngine::Lease& E, DeviceFst& D, const ChainInput& in,
                              uint64_t total_labels, uint32_t n, int semantics, HostPaths* h,
                              std::unique_ptr<DevOut>* keep);
+// A chain batch's strings on the device: the offsets rebased to the batch's first element, and
+// its `elem`-byte elements (4: labels, 1: the text entry's bytes).  upload_chain queues the two
+// copies on `stream`; the caller keeps *u until the stream has been waited for.
+struct ChainUpload {
+  std::vector<uint64_t> rebased;
+  std::unique_ptr<DevBuf> data, off;
+  uint64_t total = 0;
+  uint32_t max_len = 0;
+};
+FstError upload_chain(const void* data, size_t elem, const uint64_t* offsets, uint32_t num,
+                      hipStream_t stream, ChainUpload* u);
 bool alloc_result(FstBatchResult* out, uint32_t num, uint64_t tot);
 bool alloc_text_result(FstTextResult* out, uint32_t num, uint64_t tot);
 // Runs `compute` (the engines: it fills S.keep and, for pipelines, S.fail) over the shards
@@ -214,12 +252,38 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
 FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
                      const std::vector<double>& cost, const ShardCompute& compute,
                      FstTextResult* out);
-// ... into a lattice result (fst_compose_frozen_batch): compact_lattices on the device, both
-// offset arrays rebased per shard.
-FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
-                     const std::vector<double>& cost, const ShardCompute& compute,
-                     FstLatticeBatch* out);
-bool alloc_lattice_result(FstLatticeBatch* out, uint32_t num, uint64_t states, uint64_t arcs);
+FstError run_pipelined(int dev, FrozenFst& b, const uint32_t* labels, const uint64_t* offsets,
+                       uint32_t num, uint32_t n, int semantics, uint32_t parts,
+                       FstBatchResult* out);
+// The compute steps of a chain shard: a pipeline's stages from labels or from bytes.  `offsets`
+// are the caller's, indexed from the shard's first string.
+using Stages = std::vector<std::shared_ptr<FrozenFst>>;
+FstError run_pipeline_shard(Shard& S, const Stages& fs, const uint32_t* labels,
+                            const uint64_t* offsets, uint32_t n, int semantics);
+FstError run_text_shard(Shard& S, const Stages& fs, const uint8_t* text, const uint64_t* offsets,
+                        int semantics);
+// S.fail of a shard whose first stage is about to run or has just finished: no failure yet.
+FstError clear_stage_failures(Shard& S);
+// The stages [first, fs.size()) of one shard, from a finished stage: S.keep holds stage
+// first - 1's outputs (whatever entry produced them: a chain stage, a general-lhs batch) and
+// S.fail the failures so far.  Each stage's 1-best output tape is projected into the next
+// stage's chain inputs on the device.
+FstError run_stages_after(Shard& S, const Stages& fs, size_t first, uint32_t n, int semantics,
+                          HostPaths* h);
+
+// ---- batch_lhs.cpp: general lhs, and the lattice batch with its own arena ----
+// The compute steps of a shard of general lhs; `L` is the caller's batch, the shard its items
+// [S.s0, S.s1), staged into one block and uploaded with one DMA (stage_lhs_items).
+FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n, int semantics);
+// ... and a pipeline on a general first stage: run_lhs_shard on fs[0], then the chain stages
+// fs[1 ..] on its 1-best output tapes (S.fail: the first failing stage, when there are several).
+FstError run_lhs_pipeline_shard(Shard& S, const Stages& fs, const FstLhsBatch& L, uint32_t n,
+                                int semantics);
+// fst_shortest_path_lhs_batch's shard: the items staged the same way, then fst_shortest_path of
+// each (DeviceEngine::run_sp_batch) into a path arena of the shard's states; S.keep = the paths.
+FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n);
+// fst_connect_lhs_batch's shard: the items staged the same way, then trimmed.
+FstError run_connect_shard(Shard& S, const FstLhsBatch& L);
 // The compute steps of a lattice shard: chains from the caller's labels, or general lhs staged
 // as run_lhs_shard stages them; S.lat = the filled arena, S.keep = the statuses.
 FstError run_lattice_chain_shard(Shard& S, FrozenFst& b, const uint32_t* labels,
@@ -233,31 +297,17 @@ FstError run_lattice_arena(DeviceEngine::Lease& E, DeviceFst& D, const ChainInpu
                            uint64_t est_arcs, std::unique_ptr<LatShard>* lat,
                            std::unique_ptr<DevOut>* keep);
 // Connect of every OK item of L's arena (kernels/lattice_trim.hpp): the sweep tier, the linear
-// tier for what it handed on, then the map and the trimmed counts in LatItem.  With L.tstart
-// (the stand-alone entry) the accessibility pass runs first.  Adds its launches and kernel time
-// to t_last_stats; synchronises `stream`.
+// tier for what it handed on, then the map and the trimmed counts in LatItem.  With
+// L.trim.start (the stand-alone entry) the accessibility pass runs first.  Adds its launches
+// and kernel time to t_last_stats; synchronises `stream`.
 FstError trim_lattices(DeviceEngine::Lease& E, const int32_t* status, LatShard& L, uint32_t num,
                        hipStream_t stream);
-// fst_connect_lhs_batch's shard: the items staged as run_lhs_shard stages them, then trimmed.
-FstError run_connect_shard(Shard& S, const FstLhsBatch& L);
-// fst_shortest_path_lhs_batch's shard: the items staged the same way, then fst_shortest_path of
-// each (DeviceEngine::run_sp_batch) into a path arena of the shard's states; S.keep = the paths.
-FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n);
-FstError run_pipelined(int dev, FrozenFst& b, const uint32_t* labels, const uint64_t* offsets,
-                       uint32_t num, uint32_t n, int semantics, uint32_t parts,
-                       FstBatchResult* out);
-// The compute steps of a shard: a pipeline's stages from labels or from bytes, a general-lhs
-// batch.  `offsets` / `L` are the caller's, indexed from the shard's first string.
-using Stages = std::vector<std::shared_ptr<FrozenFst>>;
-FstError run_pipeline_shard(Shard& S, const Stages& fs, const uint32_t* labels,
-                            const uint64_t* offsets, uint32_t n, int semantics);
-FstError run_text_shard(Shard& S, const Stages& fs, const uint8_t* text, const uint64_t* offsets,
-                        int semantics);
-FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n, int semantics);
-// ... and a pipeline on a general first stage: run_lhs_shard on fs[0], then the chain stages
-// fs[1 ..] on its 1-best output tapes (S.fail: the first failing stage, when there are several).
-FstError run_lhs_pipeline_shard(Shard& S, const Stages& fs, const FstLhsBatch& L, uint32_t n,
-                                int semantics);
+// run_sharded into a lattice result (fst_compose_frozen_batch): compact_lattices on the device,
+// both offset arrays rebased per shard.
+FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
+                     const std::vector<double>& cost, const ShardCompute& compute,
+                     FstLatticeBatch* out);
+bool alloc_lattice_result(FstLatticeBatch* out, uint32_t num, uint64_t states, uint64_t arcs);
 
 // ---- c_api.cpp: a chain batch from host arrays on the engine `E` leases; fills `h` in input
 // order (small batches in one block, see run_small_batch), or keeps the device outputs ----

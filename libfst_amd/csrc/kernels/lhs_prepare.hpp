@@ -1,5 +1,5 @@
 // lhs_prepare.hpp -- on-device preparation of a device-resident batch of general lhs
-// (fst_device_compose_shortest_path_lhs): what run_lhs_shard (batch_sharded.cpp) computes on
+// (fst_device_compose_shortest_path_lhs): what run_lhs_shard (batch_lhs.cpp) computes on
 // the host while it stages a batch, computed where the batch already is.
 //
 // lhs_prepare_kernel: one wavefront per item, grid-stride over the items.  Per item it

@@ -1,6 +1,6 @@
 // lattice_trim.hip -- the launches of the lattice trim (kernels/lattice_trim.hpp): connect of
 // every item of a lattice arena, for FST_LATTICE_CONNECT on the three lattice entries and for
-// fst_connect_lhs_batch.  host::trim_lattices (batch_sharded.cpp) drives them.
+// fst_connect_lhs_batch.  host::trim_lattices (batch_lhs.cpp) drives them.
 #include <algorithm>
 
 #include "device_engine.hpp"

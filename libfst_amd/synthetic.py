@@ -140,6 +140,26 @@ def confusion_network(rng, text, max_alts=3, skip_prob=0.1):
     return 0, finals, arcs
 
 
+def edge_networks():
+    """One small fixed batch for the lhs batch entries' host layer: 48 confusion networks of 3 to
+    10 positions with up to 3 alternatives each, among them two with a negative weight (items 5
+    and 17: the replay list), one with a NaN (9), one without states (13), one of one state (21)
+    and one with a dead end (29: a state that reaches no final state, for connect)."""
+    import numpy as np
+    rng = np.random.default_rng(4848)
+    fsts = [confusion_network(rng, t, 3, 0.1) for t in utterances(rng, 48, 3, 10)]
+    for i, w in ((5, -0.5), (17, -0.5), (9, float("nan"))):
+        il, ol, _, nx = fsts[i][2][1][0]
+        fsts[i][2][1][0] = (il, ol, w, nx)
+    fsts[13] = (None, [], [])
+    fsts[21] = (0, [0.0], [[]])
+    _, finals, arcs = fsts[29]
+    arcs[0].append((lab("a"), lab("a"), 0.25, len(finals)))
+    finals.append(INF)
+    arcs.append([])
+    return fsts
+
+
 def nbest_union(rng, texts):
     """The union of n-best hypotheses as a prefix tree: one arc per byte (byte + 1 on both
     tapes) with a random per-arc cost, one final state per distinct hypothesis with a random

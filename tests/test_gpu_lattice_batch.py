@@ -18,7 +18,9 @@ import torch
 import libfst_amd as F
 import libfst_amd.fst as FF
 import oracle_ffi as O
-from test_gpu_lhs_batch import batch_of, bits, expect, got_item
+from libfst_amd import synthetic as SY
+from test_gpu_lhs_batch import (assert_shards_do_not_show, batch_of, bits, expect, got_item,
+                                tagger_rhs)
 from test_gpu_lhs_device import DeviceOut
 from test_gpu_parity import load_blob, random_rhs, to_product
 
@@ -338,6 +340,17 @@ def test_three_shards_equal_one(forty):
     one, _ = check_chain(rhs, blob, seqs, exp=exp_chain)
     three, _ = check_chain(rhs, blob, seqs, exp=exp_chain, devices=[0], shards=3)
     same_bytes(one, three)
+
+
+@pytest.mark.parametrize("project_connect", [False, True])
+def test_shards_do_not_show_on_the_edge_batch(project_connect):
+    rhs = tagger_rhs()
+    lhs = F.LhsBatch.from_fsts(SY.edge_networks())
+    one = assert_shards_do_not_show(lambda **kw: F.compose_frozen_lhs_batch(
+        rhs, lhs, project_output=project_connect, connect=project_connect, **kw))
+    assert one.status.tolist().count(F.FST_PATH_OK) >= 44
+    assert int(one.status[9]) == F.FST_PATH_UNSUPPORTED                        # (9: the NaN)
+    assert int(one.state_offsets[-1]) > 100 and int(one.arc_offsets[-1]) > 200
 
 
 # ---- 7. projection -----------------------------------------------------------------------------

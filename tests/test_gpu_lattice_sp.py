@@ -20,7 +20,8 @@ import libfst_amd.fst as FF
 import oracle_ffi as O
 from libfst_amd import synthetic as SY
 from test_gpu_lattice_batch import DeviceLattices, dev_tensor
-from test_gpu_lhs_batch import batch_of, bits, got_item, same_result
+from test_gpu_lhs_batch import (assert_shards_do_not_show, batch_of, bits, got_item,
+                                same_result)
 from test_gpu_lhs_device import DeviceLhs, DeviceOut
 from test_gpu_parity import load_blob
 
@@ -417,6 +418,14 @@ def test_grid_and_shards_do_not_show(graphs, edges, monkeypatch):
     for name in ("status", "offsets", "ilabels", "olabels", "weights", "finals"):
         assert getattr(base, name).tobytes() == getattr(sharded, name).tobytes(), name
         assert getattr(base, name).tobytes() == getattr(one, name).tobytes(), name
+
+
+def test_shards_do_not_show_on_the_edge_batch():
+    lhs = F.LhsBatch.from_fsts(SY.edge_networks())
+    one = assert_shards_do_not_show(lambda **kw: F.shortest_path_lhs_batch(lhs, 1, **kw))
+    st = one.status.tolist()
+    assert st[13] == EMPTY and st[21] == OK and st.count(OK) >= 45           # (13: no states)
+    assert int(one.offsets[22]) == int(one.offsets[21])                       # one state: no arc
 
 
 # ---- 10. device entry ----------------------------------------------------------------------------

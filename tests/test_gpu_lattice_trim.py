@@ -23,7 +23,8 @@ from libfst_amd import synthetic as SY
 from test_gpu_lattice_batch import (ARRAYS, DeviceLattices, assert_layout, chain_fst, check_chain,
                                     check_lhs, csr_of, dev_tensor, heap_tree, loop_rhs, oracle,
                                     projected, route_cols, same_bytes)
-from test_gpu_lhs_batch import batch_of, bits, expect, got_item, item
+from test_gpu_lhs_batch import (assert_shards_do_not_show, batch_of, bits, expect, got_item,
+                                item)
 from test_gpu_parity import load_blob, random_rhs
 
 pytestmark = pytest.mark.gpu
@@ -383,6 +384,16 @@ def test_grid_arena_and_shards_do_not_show(forty, graphs, monkeypatch):
     same_bytes(plain, check_lhs_connect(rhs, fsts, exp, devices=[0], shards=3))
     same_bytes(plain_chain, check_chain_connect(rhs, seqs, exp_chain, devices=[0], shards=3))
     same_bytes(plain_alone, check_connect(alone_fsts, exp=alone_exp, devices=[0], shards=3)[0])
+
+
+def test_shards_do_not_show_on_the_edge_batch():
+    fsts = SY.edge_networks()
+    lhs = F.LhsBatch.from_fsts(fsts)
+    one = assert_shards_do_not_show(lambda **kw: F.connect_lhs_batch(lhs, **kw))
+    assert one.status.tolist() == [F.FST_PATH_OK] * 48
+    ns = np.diff(one.state_offsets.astype(np.int64)).tolist()
+    assert ns[13] == 0 and ns[21] == 1 and ns[29] == len(fsts[29][1]) - 1   # (29: the dead end)
+    assert ns[:5] == [len(f[1]) for f in fsts[:5]]
 
 
 # ---- 7. device entry ---------------------------------------------------------------------------

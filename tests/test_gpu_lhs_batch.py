@@ -387,6 +387,51 @@ def test_three_shards_equal_one(forty, sem):
         assert getattr(one, name).tobytes() == getattr(three, name).tobytes(), name
 
 
+def assert_shards_do_not_show(call):
+    """`call(**kw)` is one entry on SY.edge_networks(): 2 and 3 shards on one GPU return the
+    one-shard call's arrays, byte for byte.  Returns the one-shard result."""
+    one = call()
+    arrays = {k: v for k, v in vars(one).items() if isinstance(v, np.ndarray)}
+    assert len(arrays) >= 4 and len(one.status) == 48
+    for shards in (2, 3):
+        got = call(devices=[0], shards=shards)
+        for name, a in arrays.items():
+            assert getattr(got, name).tobytes() == a.tobytes(), (name, shards)
+    return one
+
+
+def tagger_rhs():
+    return SY.to_mutable(SY.tagger()).freeze()
+
+
+@pytest.mark.parametrize("sem", SEMS)
+def test_shards_do_not_show_on_the_edge_batch(sem):
+    rhs, fsts = tagger_rhs(), SY.edge_networks()
+    lhs = F.LhsBatch.from_fsts(fsts)
+    one = assert_shards_do_not_show(
+        lambda **kw: F.compose_frozen_shortest_path_lhs_batch(rhs, lhs, 1, sem, **kw))
+    st = one.status.tolist()
+    assert st[9] == F.FST_PATH_UNSUPPORTED and st[13] == F.FST_PATH_EMPTY   # the NaN, no states
+    assert st.count(F.FST_PATH_OK) >= 44
+    handles = []
+    for start, finals, arcs in fsts:
+        m = F.MutableFst()
+        for _ in finals:
+            m.add_state()
+        if start is not None:
+            m.set_start(start)
+        for s, fw in enumerate(finals):
+            if fw != INF:
+                m.set_final(s, fw)
+        for s, state_arcs in enumerate(arcs):
+            for a in state_arcs:
+                m.add_arc(s, *a)
+        handles.append(m)
+    via_handles = assert_shards_do_not_show(
+        lambda **kw: F.compose_frozen_shortest_path_handles_batch(rhs, handles, 1, sem, **kw))
+    assert same_result(one, via_handles)
+
+
 # ---- 11. route --------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("sem", SEMS)

@@ -15,7 +15,8 @@ import pytest
 import libfst_amd as F
 import oracle_ffi as O
 from libfst_amd import synthetic as SY
-from test_gpu_lhs_batch import batch_of, bits, expect, got_item, same_result
+from test_gpu_lhs_batch import (assert_shards_do_not_show, batch_of, bits, expect, got_item,
+                                same_result, tagger_rhs)
 from test_gpu_parity import csr, expected_status, load_blob
 
 pytestmark = pytest.mark.gpu
@@ -281,6 +282,17 @@ def test_three_shards_equal_one(standins, sem):
         assert getattr(one, name).tobytes() == getattr(three, name).tobytes(), name
     assert same_text(check_text(two, fsts, sem, exp),
                      check_text(two, fsts, sem, exp, devices=[0], shards=3))
+
+
+@pytest.mark.parametrize("sem", SEMS)
+def test_shards_do_not_show_on_the_edge_batch(sem):
+    stages = [tagger_rhs(), SY.to_mutable(SY.verbalizer()).freeze()]
+    lhs = F.LhsBatch.from_fsts(SY.edge_networks())
+    labels = assert_shards_do_not_show(
+        lambda **kw: F.pipeline_lhs_batch(stages, lhs, 1, sem, **kw))
+    text = assert_shards_do_not_show(lambda **kw: F.normalize_lhs_batch(stages, lhs, sem, **kw))
+    assert labels.status.tolist() == text.status.tolist()
+    assert labels.status.tolist().count(OK) >= 40 and int(labels.status[9]) != OK   # (9: the NaN)
 
 
 @pytest.mark.parametrize("sem", SEMS)
