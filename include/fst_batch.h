@@ -464,6 +464,84 @@ FstError fst_device_emit_text(const FstDeviceBatch* stage, uint32_t num_strings,
  * decreasing path offsets. */
 FstError fst_batch_result_to_text(const FstBatchResult* in, FstTextResult* out);
 
+/* Text in, text out, with the input span of every output byte: which bytes of string i became
+ * which bytes of its normalised text (SSML marks and word boundaries across "7" -> "seven", a
+ * recogniser's word timestamps through ITN, an editor's highlights).
+ *
+ * For an OK string, output byte j gets the half-open interval [in_begin[j], in_end[j]) of the
+ * string's own input bytes; indices are relative to the string, 0 <= begin <= end <= length,
+ * and j runs over text_offsets as the text does.
+ *   One stage.  Along the path's arcs a_0 .. a_{L-1}, with nz(x) = (x != 0): the arc a_k that
+ *     emits the q-th non-epsilon olabel gives b[q] = sum_{t<k} nz(il_t) and
+ *     e[q] = b[q] + nz(il_k).  An x:y arc gives a one-byte interval, an eps:y arc the empty
+ *     interval at the boundary where it was taken, a deleted input (x:eps) belongs to no output
+ *     byte.  N = sum_t nz(il_t) is what the path consumed: the string's length.
+ *   Several stages.  Stage s consumes stage s-1's projected output (fst_device_project_output).
+ *     With (B, E) the running map of stage s-1's M output symbols into the original input and
+ *     (b, e) stage s's own,  B'[q] = b < M ? B[b] : N_1,  E'[q] = e > b ? E[b] : B'[q];
+ *     (B_1, E_1) = (b_1, e_1).  The result is the last stage's map: the text's bytes and its
+ *     projected symbols are the same sequence, the non-epsilon olabels.
+ * So begin[j] <= end[j] <= begin[j+1] and end <= length.  Non-OK strings have no bytes and no
+ * entries. */
+typedef struct {
+    uint32_t num_strings;
+    int32_t* status;          /* as FstTextResult */
+    uint64_t* text_offsets;
+    uint8_t* text;
+    double* total_weight;
+    uint64_t total_bytes;
+    uint32_t* in_begin;       /* [total_bytes] */
+    uint32_t* in_end;         /* [total_bytes] */
+} FstAlignedTextResult;
+
+/* fst_normalize_text_batch plus the two maps.  The same argument checks and zeroing of *out,
+ * the same FST_BATCH_DEVICES sharding (a sharded result is byte-identical to a one-shard run);
+ * text, offsets, statuses and total weights are byte-identical to fst_normalize_text_batch on
+ * the same call.  Always the sharded route: every stage's paths stay on the device, each
+ * finished stage's map is composed into a running one (8 B per projected symbol), and two
+ * more arrays come down.  Freed with fst_aligned_text_result_free. */
+FstError fst_normalize_text_aligned_batch(const FstHandle* stages, uint32_t num_stages,
+                                          const uint8_t* text, const uint64_t* offsets,
+                                          uint32_t num_strings, const FstBatchOptions* opts,
+                                          FstAlignedTextResult* out);
+void fst_aligned_text_result_free(FstAlignedTextResult* r);
+
+/* The device-resident pieces (every d_ pointer is device memory on the current device; both
+ * asynchronous on `stream`).
+ * fst_device_path_alignment: one stage's (b, e) per output symbol.  d_offsets [num_strings + 1]
+ * are those fst_device_emit_text or fst_device_project_output wrote for the same stage: string
+ * i owns the entries [d_offsets[i], d_offsets[i+1]) of d_begin and d_end, and d_consumed[i]
+ * receives N.  A string whose entries are not its path's symbols (not OK, an olabel above 256:
+ * no bytes in a text, the one dead label in a projection) gets [0, 0) on its entries and N = 0.
+ * d_offsets must come from that call on this same `stage`, as it wrote them: the kernel reads
+ * the stage's own statuses and takes any string whose entry count is not the count of its
+ * path's non-epsilon olabels (offsets of another stage, or changed by a status mask of the
+ * caller's) for a failed one, whose map is zeroed without an error.
+ * No entry at or past `capacity` is written.
+ * fst_device_compose_alignment: the gather above.  String i's outer entries
+ * [d_outer_offsets[i], d_outer_offsets[i+1]) of (d_b, d_e) index its inner symbols, whose map
+ * (d_inner_begin, d_inner_end; d_inner_offsets[num_strings] entries) sits at
+ * d_inner_offsets[i]; d_consumed is stage 1's.  The result goes to d_out_begin / d_out_end at
+ * the outer offsets; they may be d_b and d_e themselves.  No entry at or past `capacity` is
+ * read or written. */
+FstError fst_device_path_alignment(const FstDeviceBatch* stage, uint32_t num_strings,
+                                   const uint64_t* d_offsets, uint32_t* d_begin,
+                                   uint32_t* d_end, uint64_t capacity, uint32_t* d_consumed,
+                                   void* stream);
+FstError fst_device_compose_alignment(uint32_t num_strings, const uint64_t* d_outer_offsets,
+                                      const uint32_t* d_b, const uint32_t* d_e,
+                                      const uint64_t* d_inner_offsets,
+                                      const uint32_t* d_inner_begin,
+                                      const uint32_t* d_inner_end, const uint32_t* d_consumed,
+                                      uint32_t* d_out_begin, uint32_t* d_out_end,
+                                      uint64_t capacity, void* stream);
+
+/* Host conversion of a one-stage label result to aligned text: fst_batch_result_to_text plus
+ * the one-stage map from the result's ilabels, same semantics, no GPU needed (freed with
+ * fst_aligned_text_result_free).  FST_INVALID_ARG for a null argument or decreasing path
+ * offsets. */
+FstError fst_batch_result_to_aligned_text(const FstBatchResult* in, FstAlignedTextResult* out);
+
 /* Bring a frozen FST's device copy up on `device` (blob H2D + on-device SoA mirror). */
 FstError fst_device_prepare(FstHandle b, int32_t device);
 /* Adopt a blob that already sits in device memory on `device` (e.g. received by an

@@ -14,4 +14,6 @@ from .fst import (  # noqa: F401
     compose_frozen_shortest_path_handles_batch, normalize_lhs_batch, pipeline_lhs_batch,
     FST_LATTICE_PROJECT_OUTPUT, FST_PATH_INTERNAL, FstDeviceLattices, FstLatticeBatch,
     LatticeBatch, compose_frozen_batch, compose_frozen_lhs_batch,
-    FST_LATTICE_CONNECT, connect_lhs_batch, shortest_path_lhs_batch)
+    FST_LATTICE_CONNECT, connect_lhs_batch, shortest_path_lhs_batch,
+    AlignedTextResult, FstAlignedTextResult, batch_result_to_aligned_text,
+    normalize_text_aligned_batch)

@@ -156,6 +156,15 @@ FstError empty_result(FstTextResult* out) {
   return FST_OK;
 }
 
+FstError empty_result(FstAlignedTextResult* out) {
+  if (!alloc_aligned_text_result(out, 0, 0)) {
+    fst_aligned_text_result_free(out);
+    return FST_OOM;
+  }
+  out->text_offsets[0] = 0;
+  return FST_OK;
+}
+
 // ... of the lattice entries: no item, state_offsets = {0}, arc_offsets = {0}.
 FstError empty_result(FstLatticeBatch* out) {
   if (!alloc_lattice_result(out, 0, 0, 0)) {
@@ -774,6 +783,120 @@ FstError fst_batch_result_to_text(const FstBatchResult* in, FstTextResult* out) 
     out->total_weight[i] = w_times(d, in->final_weights[i]);
   }
   out->text_offsets[num] = w;
+  return FST_OK;
+}
+
+// ---- Aligned text entries (fst_batch.h) -------------------------------------------------
+
+FstError fst_normalize_text_aligned_batch(const FstHandle* stages, uint32_t num_stages,
+                                          const uint8_t* text, const uint64_t* offsets,
+                                          uint32_t num_strings, const FstBatchOptions* opts,
+                                          FstAlignedTextResult* out) {
+  if (!out || !stages || num_stages == 0 || !offsets ||
+      (!text && num_strings && offsets[num_strings] != offsets[0]))
+    return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!offsets_monotone(offsets, num_strings) || !flags_ok(opts)) return FST_INVALID_ARG;
+  Stages fs;
+  if (!get_stages(stages, num_stages, &fs)) return FST_INVALID_ARG;
+  if (num_strings == 0) return empty_result(out);  // nothing to run
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  const int semantics = call.semantics;
+  // (the sharded route alone: the streamed route's pull kernels write no ilabels)
+  const FstError e = run_sharded(
+      call.devices, call.nsh, num_strings, chain_costs(*fs[0], offsets, num_strings, call.nsh),
+      [&](Shard& S) {
+        S.align = std::make_unique<AlignMap>();
+        return run_text_shard(S, fs, text, offsets + S.s0, semantics);
+      },
+      out);
+  return call.close(e, "fst_normalize_text_aligned_batch", out, fst_aligned_text_result_free);
+}
+
+void fst_aligned_text_result_free(FstAlignedTextResult* r) {
+  if (!r) return;
+  pin_release(r->status);
+  pin_release(r->text_offsets);
+  pin_release(r->text);
+  pin_release(r->total_weight);
+  pin_release(r->in_begin);
+  pin_release(r->in_end);
+  std::memset(r, 0, sizeof(*r));
+}
+
+FstError fst_device_path_alignment(const FstDeviceBatch* o, uint32_t num_strings,
+                                   const uint64_t* d_offsets, uint32_t* d_begin,
+                                   uint32_t* d_end, uint64_t capacity, uint32_t* d_consumed,
+                                   void* stream) {
+  if (!o || !d_offsets || (num_strings && !d_consumed) || (capacity && (!d_begin || !d_end)))
+    return FST_INVALID_ARG;
+  hipStream_t s = nullptr;
+  DeviceEngine::Lease E = current_engine(stream, &s);
+  if (!E) return FST_INVALID_ARG;
+  return E->align_write(dev_out(o), num_strings, d_offsets, d_begin, d_end, capacity, d_consumed,
+                        s) == hipSuccess
+             ? FST_OK
+             : FST_OOM;
+}
+
+FstError fst_device_compose_alignment(uint32_t num_strings, const uint64_t* d_outer_offsets,
+                                      const uint32_t* d_b, const uint32_t* d_e,
+                                      const uint64_t* d_inner_offsets,
+                                      const uint32_t* d_inner_begin,
+                                      const uint32_t* d_inner_end, const uint32_t* d_consumed,
+                                      uint32_t* d_out_begin, uint32_t* d_out_end,
+                                      uint64_t capacity, void* stream) {
+  if (!d_outer_offsets || !d_inner_offsets || (num_strings && !d_consumed) ||
+      (capacity && (!d_b || !d_e || !d_out_begin || !d_out_end)))
+    return FST_INVALID_ARG;
+  hipStream_t s = nullptr;
+  DeviceEngine::Lease E = current_engine(stream, &s);
+  if (!E) return FST_INVALID_ARG;
+  return E->align_compose(num_strings, d_outer_offsets, d_b, d_e, d_inner_offsets, d_inner_begin,
+                          d_inner_end, d_consumed, d_out_begin, d_out_end, capacity,
+                          s) == hipSuccess
+             ? FST_OK
+             : FST_OOM;
+}
+
+FstError fst_batch_result_to_aligned_text(const FstBatchResult* in, FstAlignedTextResult* out) {
+  if (!in || !out) return FST_INVALID_ARG;
+  const uint32_t num = in->num_strings;
+  if (num && (!in->status || !in->path_offsets || !in->final_weights)) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!offsets_monotone(in->path_offsets, num)) return FST_INVALID_ARG;
+  if (num && in->path_offsets[num] != in->path_offsets[0] &&
+      (!in->ilabels || !in->olabels || !in->weights))
+    return FST_INVALID_ARG;
+  // the text first (statuses, offsets, bytes, the fold), then the map of every OK string
+  FstTextResult t;
+  if (FstError e = fst_batch_result_to_text(in, &t); e != FST_OK) return e;
+  out->num_strings = t.num_strings;
+  out->status = t.status;
+  out->text_offsets = t.text_offsets;
+  out->text = t.text;
+  out->total_weight = t.total_weight;
+  out->total_bytes = t.total_bytes;
+  out->in_begin = (uint32_t*)pin_alloc(std::max<uint64_t>(t.total_bytes, 1) * 4);
+  out->in_end = (uint32_t*)pin_alloc(std::max<uint64_t>(t.total_bytes, 1) * 4);
+  if (!out->in_begin || !out->in_end) {
+    fst_aligned_text_result_free(out);
+    return FST_OOM;
+  }
+  for (uint32_t i = 0; i < num; ++i) {
+    if (out->status[i] != kPathOk) continue;
+    uint64_t w = out->text_offsets[i];
+    uint32_t b = 0;
+    for (uint64_t k = in->path_offsets[i]; k < in->path_offsets[i + 1]; ++k) {
+      const uint32_t step = in->ilabels[k] != kEpsilon;
+      if (in->olabels[k] != kEpsilon) {
+        out->in_begin[w] = b;
+        out->in_end[w++] = b + step;
+      }
+      b += step;
+    }
+  }
   return FST_OK;
 }
 

@@ -160,6 +160,68 @@ FstError shard_text_download(Shard& S, FstTextResult* out, uint64_t byte_base) {
   return FST_OK;
 }
 
+// ---- Aligned text results (fst_normalize_text_aligned_batch) ---------------------------
+// shard_text, then the last stage's (b, e) at the text offsets (the text's bytes and the
+// projected symbols are one sequence) composed through the running map of the stages before
+// it (S.align: empty for one stage, whose own map is the result).
+FstError shard_text_aligned(Shard& S) {
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  const DevOut& o = *S.keep;
+  S.st = std::make_unique<DevBuf>(num * 4ull);
+  S.off = std::make_unique<DevBuf>((num + 1ull) * 8);
+  S.fin = std::make_unique<DevBuf>(num * 8ull);
+  if (!S.st->p || !S.off->p || !S.fin->p) return FST_OOM;
+  if (S.E->text_count(o.v, num, S.fail ? (const int32_t*)S.fail->p : nullptr, (int32_t*)S.st->p,
+                      (uint64_t*)S.off->p, (double*)S.fin->p, &S.tot, stream) != hipSuccess)
+    return FST_OOM;
+  S.text = std::make_unique<DevBuf>(S.tot);
+  S.in_begin = std::make_unique<DevBuf>(std::max<uint64_t>(S.tot, 1) * 4);
+  S.in_end = std::make_unique<DevBuf>(std::max<uint64_t>(S.tot, 1) * 4);
+  DevBuf consumed(num * 4ull);
+  if (!S.text->p || !S.in_begin->p || !S.in_end->p || !consumed.p) return FST_OOM;
+  // every return below waits for the stream before `consumed`, the arena and the running map
+  // go back to the pool
+  StreamDrain drain{{stream}};
+  uint32_t* b = (uint32_t*)S.in_begin->p;
+  uint32_t* e = (uint32_t*)S.in_end->p;
+  if (S.E->text_write(o.v, num, (const int32_t*)S.st->p, (const uint64_t*)S.off->p,
+                      (uint8_t*)S.text->p, S.tot, stream) != hipSuccess ||
+      S.E->align_write(o.v, num, (const uint64_t*)S.off->p, b, e, S.tot, (uint32_t*)consumed.p,
+                       stream) != hipSuccess)
+    return FST_OOM;
+  const AlignMap& run = *S.align;
+  if (run.b && S.E->align_compose(num, (const uint64_t*)S.off->p, b, e,
+                                  (const uint64_t*)run.off->p, (const uint32_t*)run.b->p,
+                                  (const uint32_t*)run.e->p, (const uint32_t*)run.n1->p, b, e,
+                                  S.tot, stream) != hipSuccess)
+    return FST_OOM;
+  // (synchronised: the download may run on another engine's stream)
+  if (hipStreamSynchronize(stream) != hipSuccess) return FST_OOM;
+  drain.done = true;
+  S.align.reset();
+  S.keep.reset();  // the path arena is not downloaded
+  return FST_OK;
+}
+
+// The text's four arrays, and the two maps at the shard's first byte: their indices are per
+// string, so nothing is rebased.
+FstError shard_text_aligned_download(Shard& S, FstAlignedTextResult* out, uint64_t byte_base) {
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  if (!(d2h(out->status + S.s0, S.st->p, num * 4ull, stream) &&
+        d2h(out->total_weight + S.s0, S.fin->p, num * 8ull, stream) &&
+        d2h(out->text_offsets + S.s0, S.off->p, num * 8ull, stream) &&
+        d2h(out->text + byte_base, S.text->p, S.tot, stream) &&
+        d2h(out->in_begin + byte_base, S.in_begin->p, S.tot * 4, stream) &&
+        d2h(out->in_end + byte_base, S.in_end->p, S.tot * 4, stream)) ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return FST_OOM;
+  if (byte_base)
+    for (uint32_t i = S.s0; i < S.s1; ++i) out->text_offsets[i] += byte_base;
+  return FST_OK;
+}
+
 
 // One chain stage of a shard on device inputs: S.keep = its outputs (`h`: the statuses, one
 // pinned block for all the stages of a shard).
@@ -187,6 +249,45 @@ FstError clear_stage_failures(Shard& S) {
   return FST_OK;
 }
 
+namespace {
+
+// The aligned text entry between two stages: the finished stage's (b, e, N) at its projection
+// offsets `off` (`total` symbols), composed into the running map S.align, which it replaces.
+// Synchronises the shard's stream on every return past the allocations: the stage that follows
+// hands the arena these kernels read back to the pool, and so does this with the map it replaces.
+FstError align_projected(Shard& S, const DevBuf& off, uint64_t total) {
+  const uint32_t num = S.s1 - S.s0;
+  const hipStream_t stream = S.E.stream();
+  AlignMap& run = *S.align;
+  AlignMap next;
+  next.off = std::make_unique<DevBuf>((num + 1ull) * 8);
+  next.b = std::make_unique<DevBuf>(std::max<uint64_t>(total, 1) * 4);
+  next.e = std::make_unique<DevBuf>(std::max<uint64_t>(total, 1) * 4);
+  next.n1 = std::make_unique<DevBuf>(num * 4ull);
+  if (!next.off->p || !next.b->p || !next.e->p || !next.n1->p) return FST_OOM;
+  StreamDrain drain{{stream}};  // (declared after `next`: its blocks outlive the kernels)
+  uint32_t* nb = (uint32_t*)next.b->p;
+  uint32_t* ne = (uint32_t*)next.e->p;
+  if (hipMemcpyAsync(next.off->p, off.p, (num + 1ull) * 8, hipMemcpyDeviceToDevice, stream) !=
+          hipSuccess ||
+      S.E->align_write(S.keep->v, num, (const uint64_t*)off.p, nb, ne, total,
+                       (uint32_t*)next.n1->p, stream) != hipSuccess)
+    return FST_OOM;
+  if (run.b) {
+    if (S.E->align_compose(num, (const uint64_t*)off.p, nb, ne, (const uint64_t*)run.off->p,
+                           (const uint32_t*)run.b->p, (const uint32_t*)run.e->p,
+                           (const uint32_t*)run.n1->p, nb, ne, total, stream) != hipSuccess)
+      return FST_OOM;
+    next.n1.swap(run.n1);  // n1 stays stage 1's
+  }
+  if (hipStreamSynchronize(stream) != hipSuccess) return FST_OOM;
+  drain.done = true;
+  run = std::move(next);  // (the map it replaces goes back to the pool: nothing reads it now)
+  return FST_OK;
+}
+
+}  // namespace
+
 FstError run_stages_after(Shard& S, const Stages& fs, size_t first, uint32_t n, int semantics,
                           HostPaths* h) {
   DeviceEngine::Lease& E = S.E;
@@ -210,6 +311,9 @@ FstError run_stages_after(Shard& S, const Stages& fs, size_t first, uint32_t n, 
     // (synchronises: pst may go back to the pool)
     uint64_t in_total = 0;
     if (!read_u64(&in_total, (uint64_t*)off.p + num_strings, stream)) return FST_OOM;
+    // (before the stage resets S.keep: the map reads the finished stage's arena)
+    if (S.align)
+      if (FstError e = align_projected(S, off, in_total); e != FST_OK) return e;
     if (t_prof) t_prof->lap(4);
     // (the stage synchronises the stream before lab and off go back to the pool)
     if (FstError e = run_chain_stage(S, *fs[k], lab, off, in_total, max_len, n, semantics, h);
@@ -277,6 +381,19 @@ bool alloc_text_result(FstTextResult* out, uint32_t num, uint64_t tot) {
   out->total_weight = (double*)pin_alloc(std::max<size_t>(num, 1) * 8);
   out->text = (uint8_t*)pin_alloc(std::max<uint64_t>(tot, 1));
   return out->status && out->text_offsets && out->total_weight && out->text;
+}
+
+bool alloc_aligned_text_result(FstAlignedTextResult* out, uint32_t num, uint64_t tot) {
+  out->num_strings = num;
+  out->total_bytes = tot;
+  out->status = (int32_t*)pin_alloc(std::max<size_t>(num, 1) * 4);
+  out->text_offsets = (uint64_t*)pin_alloc((num + 1ull) * 8);
+  out->total_weight = (double*)pin_alloc(std::max<size_t>(num, 1) * 8);
+  out->text = (uint8_t*)pin_alloc(std::max<uint64_t>(tot, 1));
+  out->in_begin = (uint32_t*)pin_alloc(std::max<uint64_t>(tot, 1) * 4);
+  out->in_end = (uint32_t*)pin_alloc(std::max<uint64_t>(tot, 1) * 4);
+  return out->status && out->text_offsets && out->total_weight && out->text && out->in_begin &&
+         out->in_end;
 }
 
 FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
@@ -398,6 +515,20 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
                        [=](uint64_t tot, uint64_t) { return alloc_text_result(out, num, tot); },
                        [=](Shard& S, uint64_t base, uint64_t) {
                          return shard_text_download(S, out, base);
+                       },
+                       [=](uint64_t tot, uint64_t) { out->text_offsets[num] = tot; }};
+  return run_sharded(devices, nsh, num, cost, compute, sink);
+}
+
+FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
+                     const std::vector<double>& cost, const ShardCompute& compute,
+                     FstAlignedTextResult* out) {
+  const ShardSink sink{shard_text_aligned,
+                       [=](uint64_t tot, uint64_t) {
+                         return alloc_aligned_text_result(out, num, tot);
+                       },
+                       [=](Shard& S, uint64_t base, uint64_t) {
+                         return shard_text_aligned_download(S, out, base);
                        },
                        [=](uint64_t tot, uint64_t) { out->text_offsets[num] = tot; }};
   return run_sharded(devices, nsh, num, cost, compute, sink);

@@ -2730,6 +2730,30 @@ hipError_t DeviceEngine::text_write(const BatchOutDev& s, uint32_t num, const in
   return hipGetLastError();
 }
 
+hipError_t DeviceEngine::align_write(const BatchOutDev& s, uint32_t num, const uint64_t* offsets,
+                                     uint32_t* begin, uint32_t* end, uint64_t cap,
+                                     uint32_t* consumed, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(dev_));
+  if (!num) return hipSuccess;
+  // (FSTAMD_ALIGN_GRID, tests: few waves, so that each takes many strings in turn)
+  const uint32_t grid = std::min<uint32_t>(std::min<uint32_t>(num, (uint32_t)num_cus_ * 32),
+                                           grid_cap("FSTAMD_ALIGN_GRID"));
+  return launch_align_write(s, num, offsets, begin, end, cap, consumed, grid, stream);
+}
+
+hipError_t DeviceEngine::align_compose(uint32_t num, const uint64_t* outer_off, const uint32_t* b,
+                                       const uint32_t* e, const uint64_t* inner_off,
+                                       const uint32_t* in_begin, const uint32_t* in_end,
+                                       const uint32_t* n1, uint32_t* out_begin,
+                                       uint32_t* out_end, uint64_t cap, hipStream_t stream) {
+  HIP_TRY(hipSetDevice(dev_));
+  if (!num) return hipSuccess;
+  const uint32_t grid = std::min<uint32_t>(std::min<uint32_t>(num, (uint32_t)num_cus_ * 32),
+                                           grid_cap("FSTAMD_ALIGN_GRID"));
+  return launch_align_compose(num, outer_off, b, e, inner_off, in_begin, in_end, n1, out_begin,
+                              out_end, cap, grid, stream);
+}
+
 hipError_t DeviceEngine::text_fixup(const BatchOutDev& s, const TextOutDev& tx,
                                     const int32_t* first, uint32_t num, hipStream_t stream) {
   HIP_TRY(hipSetDevice(dev_));

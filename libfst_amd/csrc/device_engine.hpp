@@ -534,6 +534,15 @@ hipError_t launch_sp_frontier(const LatSpDev& p, const BatchOutDev& out, uint32_
                               hipStream_t stream);
 hipError_t launch_sp_replay(const LatSpDev& p, const uint32_t* items, uint32_t count,
                             const BatchOutDev& out, uint32_t grid, hipStream_t stream);
+// ---- input spans per output symbol (text_align.hip, kernels/text_align.hpp) ----
+hipError_t launch_align_write(const BatchOutDev& s, uint32_t num, const uint64_t* offsets,
+                              uint32_t* begin, uint32_t* end, uint64_t cap, uint32_t* consumed,
+                              uint32_t grid, hipStream_t stream);
+hipError_t launch_align_compose(uint32_t num, const uint64_t* outer_off, const uint32_t* b,
+                                const uint32_t* e, const uint64_t* inner_off,
+                                const uint32_t* in_begin, const uint32_t* in_end,
+                                const uint32_t* n1, uint32_t* out_begin, uint32_t* out_end,
+                                uint64_t cap, uint32_t grid, hipStream_t stream);
 // On-device preparation of a device-resident batch (kernels/lhs_prepare.hpp; lhs_batch.hip
 // holds the instances).  In: the caller's arrays in FstLhsBatch's layout, all device memory,
 // and their two extents as the host read them.  Out: descriptors, local arc offsets
@@ -758,6 +767,21 @@ class DeviceEngine {
   // past `cap` is written.  Asynchronous on `stream`.
   hipError_t text_write(const BatchOutDev& s, uint32_t num, const int32_t* status,
                         const uint64_t* offsets, uint8_t* text, uint64_t cap, hipStream_t stream);
+  // Input spans per output symbol (kernels/text_align.hpp).  align_write: a finished stage's
+  // (b, e) per non-epsilon olabel at offsets[i] + rank -- `offsets` [num + 1] are text_count's
+  // or project_output's for that stage -- and consumed[i] = the non-epsilon ilabels of the
+  // path; a string whose entries are not its path's (no bytes, a dead label) gets [0, 0) and
+  // 0.  No entry at or past `cap` is written.  align_compose: the gather of the outer stage's
+  // (b, e) through the running map (in_begin, in_end at inner_off) of the stage before it;
+  // out_* may be b and e themselves.  Both asynchronous on `stream`.
+  hipError_t align_write(const BatchOutDev& s, uint32_t num, const uint64_t* offsets,
+                         uint32_t* begin, uint32_t* end, uint64_t cap, uint32_t* consumed,
+                         hipStream_t stream);
+  hipError_t align_compose(uint32_t num, const uint64_t* outer_off, const uint32_t* b,
+                           const uint32_t* e, const uint64_t* inner_off,
+                           const uint32_t* in_begin, const uint32_t* in_end, const uint32_t* n1,
+                           uint32_t* out_begin, uint32_t* out_end, uint64_t cap,
+                           hipStream_t stream);
   // The streamed text batch's strings the pull tier handed on, once the later tiers have
   // written their paths to the arena's fixed slots: the same emission (emit_text_paths) for
   // every string whose `first` status is neither OK nor EMPTY.  Asynchronous on `stream`.

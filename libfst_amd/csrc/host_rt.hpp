@@ -181,6 +181,14 @@ struct LatShard {
   } csr;
 };
 
+// The aligned text entry's carrier through the stages of a shard (null for every other entry):
+// the running map of the last projected stage's output symbols into the string's own input --
+// 8 B per symbol, (b, e) at `off` [num + 1], a copy of that projection's offsets -- and n1, what
+// stage 1 consumed per string.  Empty (no `b`) until the first projection.
+struct AlignMap {
+  std::unique_ptr<DevBuf> off, b, e, n1;
+};
+
 struct Shard {
   int dev = 0;
   uint32_t s0 = 0, s1 = 0;
@@ -192,6 +200,10 @@ struct Shard {
   std::unique_ptr<DevBuf> st, off, fin, il, ol, w;
   std::unique_ptr<DevBuf> text;  // text entries: the emitted bytes (fin: the total weights)
   uint64_t tot = 0;              // arcs of the compacted shard (text entries: bytes)
+  // the aligned text entry: the carrier run_stages_after feeds, and the result's two maps
+  // ([tot] each, per string) beside `text`
+  std::unique_ptr<AlignMap> align;
+  std::unique_ptr<DevBuf> in_begin, in_end;
   FstError err = FST_OK;
   LaunchStats stats;
 };
@@ -237,6 +249,7 @@ FstError upload_chain(const void* data, size_t elem, const uint64_t* offsets, ui
                       hipStream_t stream, ChainUpload* u);
 bool alloc_result(FstBatchResult* out, uint32_t num, uint64_t tot);
 bool alloc_text_result(FstTextResult* out, uint32_t num, uint64_t tot);
+bool alloc_aligned_text_result(FstAlignedTextResult* out, uint32_t num, uint64_t tot);
 // Runs `compute` (the engines: it fills S.keep and, for pipelines, S.fail) over the shards
 // of a batch and gathers their results through `sink`.  Shards are contiguous string ranges of
 // equal estimated cost (cost[i]: the work estimate of string i); shard j runs on
@@ -252,6 +265,11 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
 FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
                      const std::vector<double>& cost, const ShardCompute& compute,
                      FstTextResult* out);
+// ... into an aligned text result (fst_normalize_text_aligned_batch): the same, then the input
+// span of every output byte (align_write / align_compose).  `compute` sets S.align.
+FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
+                     const std::vector<double>& cost, const ShardCompute& compute,
+                     FstAlignedTextResult* out);
 FstError run_pipelined(int dev, FrozenFst& b, const uint32_t* labels, const uint64_t* offsets,
                        uint32_t num, uint32_t n, int semantics, uint32_t parts,
                        FstBatchResult* out);
@@ -267,7 +285,8 @@ FstError clear_stage_failures(Shard& S);
 // The stages [first, fs.size()) of one shard, from a finished stage: S.keep holds stage
 // first - 1's outputs (whatever entry produced them: a chain stage, a general-lhs batch) and
 // S.fail the failures so far.  Each stage's 1-best output tape is projected into the next
-// stage's chain inputs on the device.
+// stage's chain inputs on the device.  With S.align (the aligned text entry) each finished
+// stage's input spans are composed into the running map right after its projection.
 FstError run_stages_after(Shard& S, const Stages& fs, size_t first, uint32_t n, int semantics,
                           HostPaths* h);
 

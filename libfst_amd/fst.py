@@ -49,6 +49,11 @@ class FstTextResult(C.Structure):
                 ("total_weight", C.POINTER(C.c_double)), ("total_bytes", C.c_uint64)]
 
 
+class FstAlignedTextResult(C.Structure):
+    _fields_ = FstTextResult._fields_ + [("in_begin", C.POINTER(C.c_uint32)),
+                                         ("in_end", C.POINTER(C.c_uint32))]
+
+
 FST_BATCH_DEVICES = 1
 
 
@@ -199,6 +204,16 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_u64),
                                        C.c_void_p]),
     "fst_batch_result_to_text": (C.c_int, [C.POINTER(FstBatchResult), C.POINTER(FstTextResult)]),
+    "fst_normalize_text_aligned_batch": (
+        C.c_int, [C.c_void_p, _u32, C.c_void_p, C.c_void_p, _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstAlignedTextResult)]),
+    "fst_aligned_text_result_free": (None, [C.POINTER(FstAlignedTextResult)]),
+    "fst_device_path_alignment": (C.c_int, [C.POINTER(FstDeviceBatch), _u32, _P, _P, _P, _u64, _P,
+                                            _P]),
+    "fst_device_compose_alignment": (C.c_int, [_u32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _u64,
+                                               _P]),
+    "fst_batch_result_to_aligned_text": (C.c_int, [C.POINTER(FstBatchResult),
+                                                   C.POINTER(FstAlignedTextResult)]),
     "fst_debug_text_compact": (_u64, [_u32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     "fst_debug_expand_weight_codes": (None, [C.c_void_p, _u64, C.c_void_p, C.c_void_p]),
@@ -825,6 +840,111 @@ def batch_result_to_text(r: BatchResult) -> TextResult:
     if rc != FST_OK:
         raise RuntimeError(f"fst_batch_result_to_text failed: {rc}")
     return _take_text(res)
+
+
+@dataclass
+class AlignedTextResult(TextResult):
+    """TextResult plus, per output byte, the half-open interval [in_begin, in_end) of the
+    string's own input bytes it came from (include/fst_batch.h, FstAlignedTextResult)."""
+    in_begin: np.ndarray
+    in_end: np.ndarray
+
+    def spans(self, i):
+        """String i as (in_lo, in_hi, out_lo, out_hi) segments, all relative to the string.
+        Consecutive output bytes join one segment when they carry one and the same input
+        interval (insertions at one boundary: in synthetic's cascade the five bytes of "seven"
+        all carry the empty interval [1, 1) behind the "7", since they are emitted on
+        input-epsilon arcs), or when they are copied text: one-byte intervals that advance
+        with the output."""
+        a, z = int(self.offsets[i]), int(self.offsets[i + 1])
+        segs = []  # [in_lo, in_hi, out_lo, out_hi, kind]; kind None: one byte so far
+        for j in range(a, z):
+            b, e, o = int(self.in_begin[j]), int(self.in_end[j]), j - a
+            if segs:
+                s = segs[-1]
+                if (b, e) == (s[0], s[1]) and s[4] in (None, "same"):
+                    s[3], s[4] = o + 1, "same"
+                    continue
+                if (e == b + 1 and b == s[1] and s[1] - s[0] == s[3] - s[2]
+                        and s[4] in (None, "copy")):
+                    s[1], s[3], s[4] = e, o + 1, "copy"
+                    continue
+            segs.append([b, e, o, o + 1, None])
+        return [tuple(s[:4]) for s in segs]
+
+
+class _AlignedOwner:
+    """Owns one FstAlignedTextResult; freed once no array views it."""
+
+    def __init__(self, res):
+        self.res = res
+
+    def __del__(self):
+        try:
+            lib().fst_aligned_text_result_free(C.byref(self.res))
+        except Exception:  # interpreter shutdown
+            pass
+
+
+def _take_aligned(res) -> AlignedTextResult:
+    num, tot = int(res.num_strings), int(res.total_bytes)
+    owner = _AlignedOwner(res)
+
+    def arr(p, cnt, dt, ct):
+        if cnt == 0:
+            return np.zeros(0, dt)
+        buf = (ct * cnt).from_address(C.cast(p, C.c_void_p).value)
+        buf._owner = owner  # the view keeps the result alive
+        return np.frombuffer(buf, dtype=dt)
+
+    return AlignedTextResult(status=arr(res.status, num, np.int32, C.c_int32),
+                             offsets=arr(res.text_offsets, num + 1, np.uint64, C.c_uint64),
+                             text=arr(res.text, tot, np.uint8, C.c_uint8),
+                             total_weight=arr(res.total_weight, num, np.float64, C.c_double),
+                             in_begin=arr(res.in_begin, tot, np.uint32, C.c_uint32),
+                             in_end=arr(res.in_end, tot, np.uint32, C.c_uint32))
+
+
+def normalize_text_aligned_batch(stages, texts, semantics: int = FST_SEM_LAZY, devices=None,
+                                 shards: int = 0, device: int = -1) -> AlignedTextResult:
+    """normalize_text_batch plus the input span of every output byte
+    (fst_normalize_text_aligned_batch): the same text, offsets, statuses and weights, and
+    in_begin / in_end per output byte, computed on the device from every stage's 1-best path."""
+    stages = [stages] if isinstance(stages, Fst) else list(stages)
+    data, offsets = text_csr(texts)
+    hs = (C.c_uint64 * max(len(stages), 1))(*[s.h for s in stages])
+    opts = batch_options(device, semantics, devices, shards)
+    res = FstAlignedTextResult()
+    rc = lib().fst_normalize_text_aligned_batch(hs, len(stages), data.ctypes.data,
+                                                offsets.ctypes.data, len(offsets) - 1,
+                                                C.byref(opts), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_normalize_text_aligned_batch failed: {rc}")
+    return _take_aligned(res)
+
+
+def batch_result_to_aligned_text(r: BatchResult) -> AlignedTextResult:
+    """The host conversion of a one-stage label result (fst_batch_result_to_aligned_text): what
+    normalize_text_aligned_batch returns for the same paths; runs without a GPU."""
+    status = np.ascontiguousarray(r.status, dtype=np.int32)
+    offsets = np.ascontiguousarray(r.offsets, dtype=np.uint64)
+    ilabels = np.ascontiguousarray(r.ilabels, dtype=np.uint32)
+    olabels = np.ascontiguousarray(r.olabels, dtype=np.uint32)
+    weights = np.ascontiguousarray(r.weights, dtype=np.float64)
+    finals = np.ascontiguousarray(r.finals, dtype=np.float64)
+
+    def ptr(a, ct):
+        return C.cast(a.ctypes.data, C.POINTER(ct))
+
+    src = FstBatchResult(len(status), ptr(status, C.c_int32), ptr(offsets, C.c_uint64),
+                         ptr(ilabels, C.c_uint32), ptr(olabels, C.c_uint32),
+                         ptr(weights, C.c_double), ptr(finals, C.c_double),
+                         int(offsets[-1]) if len(offsets) else 0)
+    res = FstAlignedTextResult()
+    rc = lib().fst_batch_result_to_aligned_text(C.byref(src), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_batch_result_to_aligned_text failed: {rc}")
+    return _take_aligned(res)
 
 
 def debug_text_compact(slots, nbytes, status, total_weight, text):
