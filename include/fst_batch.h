@@ -361,6 +361,70 @@ FstError fst_device_shortest_path_lhs(const FstLhsBatch* d_lhs, uint32_t n,
                                       const FstBatchOptions* opts, const FstDeviceBatch* out,
                                       void* stream);
 
+/* The n best DISTINCT PATHS of every item of an lhs batch, for ACYCLIC items: what a caller asks
+ * of a lattice before it picks a reading with a model of its own (an LM, a bias list, a UI with
+ * alternatives).  The reference has no n-best (shortestPath returns UnsupportedNShortest for
+ * n > 1, src/ops/shortest-path.zig:14-24), so the definition is this comment.  The result is an
+ * ordinary FstBatchResult of num_fsts * n strings: item i's k-th best is string i * n + k, and
+ * fst_batch_result_free, fst_batch_result_to_text and fst_batch_result_to_aligned_text work on
+ * it unchanged.
+ *
+ * Per item: states 0 .. S-1, arcs in CSR.  An arc's INDEX a is its position in the item's own
+ * arc range; it runs src(a) -> dst(a) with weight w(a).
+ * Statuses.  All n strings of an item get the same one, tested in this order:
+ *   1. no start, or zero states                                 FST_PATH_EMPTY
+ *   2. a NaN arc or final weight anywhere in the item           FST_PATH_UNSUPPORTED
+ *   3. a cycle among the states reachable from the start        FST_PATH_UNSUPPORTED
+ *      (every arc counts, whatever its weight; a self-loop is a cycle.  Such an item may have
+ *      infinitely many paths.  Compose of a chain with an rhs that has no input-epsilon cycle,
+ *      confusion networks and recogniser lattices are acyclic.)
+ *   4. (device entry) an item the prepare kernel refuses        FST_PATH_UNSUPPORTED
+ * An arc of weight +inf is never part of a path (the reference's isZero, :93).
+ * A PREFIX is a path from the start.  Its cost g is the f64 left fold ((0.0 + w_1) + w_2) + ...
+ * (:72); a prefix whose g is +inf is dropped, by overflow as well.
+ * The order of two prefixes that END IN THE SAME STATE, recursively:
+ *   1. the smaller g first, compared as f64 values (-0.0 equals +0.0);
+ *   2. then the smaller index of the last arc;
+ *   3. then, with the same last arc, the order of the two prefixes without it (both end in its
+ *      src);
+ *   4. the empty prefix at the start has no last arc and sorts after any arc at equal g (it has
+ *      no competitor in an acyclic item).
+ * A COMPLETE PATH is a prefix that ends in a state t with final(t) != +inf.  Its total is
+ * fl(g + final(t)); it is dropped if that is +inf.  Complete paths are ordered by total, then
+ * by t, then by the prefix's rank among all prefixes ending in t.
+ * String i * n + k is the k-th complete path in that order, FST_PATH_OK: its arcs are the item's
+ * own arcs (ilabel, olabel and weight bits copied), its final_weights entry is final(t), copied;
+ * the start being final gives a path of zero arcs.  An item of m < n complete paths leaves
+ * strings i * n + m .. i * n + n - 1 FST_PATH_EMPTY.  Paths are distinct as arc sequences; two
+ * may print the same text (removing those is determinisation, which is not built).
+ * How it is computed: E(t), the at most n best prefixes ending in t, each (g, a, r) = cost, last
+ * arc, rank of the rest in E(src(a)).  E(start) = [(0.0, none, 0)]; E(t) = the n smallest of
+ * {(fl(E(src(a))[r].g + w(a)), a, r)} over the arcs a into t and all r, in (g, a, r)
+ * lexicographic order.  f64 addition is monotone in either operand, so a prefix outside its
+ * state's top n is never part of a later top n; on an acyclic item every order of evaluation
+ * that finishes the predecessors first gives the same lists.
+ *
+ * The same validator as the other lhs entries runs; a failed check returns FST_INVALID_ARG
+ * with *out zeroed, as do n == 0, n > FST_NBEST_MAX, num_fsts * n >= 2^32 (these three are
+ * tested before lhs's arrays are read), a null lhs / out and unknown opts->flags.
+ * num_fsts == 0 gives the empty OK result.  opts->semantics
+ * is ignored.  FST_BATCH_DEVICES shards by arcs + 1 per item; a sharded result is in input order
+ * and byte-identical to a one-shard run.  fst_last_launch_stats reports engine 13. */
+#define FST_NBEST_MAX 16u
+FstError fst_nbest_lhs_batch(const FstLhsBatch* lhs, uint32_t n, const FstBatchOptions* opts,
+                             FstBatchResult* out);
+
+/* Device-resident, as fst_device_shortest_path_lhs: d_lhs is a host struct of device pointers
+ * with trusted extents, the prepare kernel validates the items, the call SYNCHRONISES `stream`.
+ * `out` has room for num_fsts * n strings; the arena is the caller's, strings that do not fit
+ * report FST_PATH_OUTPUT_FULL and *arc_cursor ends at what the batch needs (n * the total
+ * states of the batch always suffice: a path of an acyclic item has fewer arcs than the item has
+ * states).  The result chains into fst_device_emit_text, fst_device_project_output and
+ * fst_device_path_alignment on num_fsts * n strings.  Engine 13; `launches` counts the two
+ * preparation kernels too. */
+FstError fst_device_nbest_lhs(const FstLhsBatch* d_lhs, uint32_t n, const FstBatchOptions* opts,
+                              const FstDeviceBatch* out, void* stream);
+
 /* The device-resident form, chains in and lattices out, so that a cascade never leaves the
  * device.  Every pointer in `out` is device memory on opts->device, in FstLhsBatch's layout: a
  * host-side FstLhsBatch holding those pointers goes straight into
@@ -566,7 +630,10 @@ typedef struct {
                                    11 = fst_connect_lhs_batch (the lattice trim alone),
                                    12 = fst_shortest_path_lhs_batch and
                                         fst_device_shortest_path_lhs (one wave per lattice,
-                                        frontier and heap-replay tiers behind it) */
+                                        frontier and heap-replay tiers behind it),
+                                   13 = fst_nbest_lhs_batch and fst_device_nbest_lhs (one wave
+                                        per lattice with its tables in LDS, a workgroup per
+                                        lattice with them in HBM behind it) */
     uint32_t grid;              /* workgroups of the dominant kernel */
 } FstLaunchStats;
 FstError fst_last_launch_stats(FstLaunchStats* out);

@@ -175,6 +175,10 @@ FstError empty_result(FstLatticeBatch* out) {
   const_cast<uint64_t*>(out->fsts.arc_offsets)[0] = 0;
   return FST_OK;
 }
+// The n of the two n-best entries: 1 .. FST_NBEST_MAX, and num * n result strings index in 32 bits.
+bool nbest_slots_ok(uint32_t num, uint32_t n) {
+  return n >= 1 && n <= FST_NBEST_MAX && (uint64_t)num * n < (1ull << 32);
+}
 bool lattice_flags_ok(uint32_t f) {
   return !(f & ~(FST_LATTICE_PROJECT_OUTPUT | FST_LATTICE_CONNECT));  // (bit 1 stays unknown)
 }
@@ -191,17 +195,23 @@ std::vector<double> lhs_costs(const FstLhsBatch& lhs, uint32_t nsh) {
 // A checked batch of general lhs in shards balanced by lhs_costs: `shard` computes one (it gets
 // the call for its semantics) into a label, text or lattice result.  The empty batch is its OK
 // result before any GPU check.  `any_semantics`: the entry never looks at opts->semantics.
+// `per`: strings per item of a label result (fst_nbest_lhs_batch's n).
 template <class R, class F>
 FstError lhs_sharded(const FstLhsBatch* lhs, const FstBatchOptions* opts, bool any_semantics,
-                     R* out, const char* name, void (*release)(R*), const F& shard) {
+                     R* out, const char* name, void (*release)(R*), const F& shard,
+                     uint32_t per = 1) {
   if (lhs->num_fsts == 0) return empty_result(out);
   BatchCall call;
   if (FstError e = call.open(opts); e != FST_OK) return e;
   if (!any_semantics && call.semantics != FST_SEM_LAZY && call.semantics != FST_SEM_EAGER)
     return FST_INVALID_ARG;
-  const FstError e =
-      run_sharded(call.devices, call.nsh, lhs->num_fsts, lhs_costs(*lhs, call.nsh),
-                  [&](Shard& S) { return shard(S, call); }, out);
+  const std::vector<double> cost = lhs_costs(*lhs, call.nsh);
+  const auto compute = [&](Shard& S) { return shard(S, call); };
+  FstError e;
+  if constexpr (std::is_same_v<R, FstBatchResult>)
+    e = run_sharded(call.devices, call.nsh, lhs->num_fsts, cost, compute, out, per);
+  else
+    e = run_sharded(call.devices, call.nsh, lhs->num_fsts, cost, compute, out);
   return call.close(e, name, out, release);
 }
 
@@ -509,6 +519,20 @@ FstError fst_shortest_path_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
                      [&](Shard& S, const BatchCall&) { return run_sp_shard(S, *lhs, n); });
 }
 
+// The n best distinct paths of every item of an lhs batch: staged as above, n strings per item
+// (run_nbest_shard; the gather moves a shard's items [s0, s1) as strings [s0 * n, s1 * n)).
+FstError fst_nbest_lhs_batch(const FstLhsBatch* lhs, uint32_t n, const FstBatchOptions* opts,
+                             FstBatchResult* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  // (n and the slot count before the validator: it reads num_fsts entries of the arrays)
+  if (!lhs || !nbest_slots_ok(lhs->num_fsts, n) || !lhs_batch_valid(lhs) || !flags_ok(opts))
+    return FST_INVALID_ARG;
+  return lhs_sharded(
+      lhs, opts, true, out, "fst_nbest_lhs_batch", fst_batch_result_free,
+      [&](Shard& S, const BatchCall&) { return run_nbest_shard(S, *lhs, n); }, n);
+}
+
 void fst_lattice_batch_free(FstLatticeBatch* r) {
   if (!r) return;
   pin_release(r->status);
@@ -624,6 +648,27 @@ FstError fst_device_shortest_path_lhs(const FstLhsBatch* d_lhs, uint32_t n,
   st.launches += p.launches;
   t_last_stats = st;
   call.drain.done = true;  // (run_sp_batch synchronised the stream)
+  return FST_OK;
+}
+
+// The n best paths of a device-resident lhs batch: prepared like the shortest path's, then
+// DeviceEngine::run_nbest_batch into the caller's arena, n strings per item.
+FstError fst_device_nbest_lhs(const FstLhsBatch* d_lhs, uint32_t n, const FstBatchOptions* opts,
+                              const FstDeviceBatch* o, void* stream) {
+  if (!device_lhs_args_ok(d_lhs) || !device_batch_out_ok(o, d_lhs->num_fsts) || !flags_ok(opts) ||
+      !nbest_slots_ok(d_lhs->num_fsts, n))
+    return FST_INVALID_ARG;
+  DeviceCall call;
+  if (FstError e = call.open(opts, nullptr, stream); e != FST_OK) return e;
+  LhsBatchDev batch;
+  LhsPrepared p;
+  if (FstError e = device_lhs_prepare(call, d_lhs, &batch, &p); e != FST_OK) return e;
+  LaunchStats st;
+  if (call.E->run_nbest_batch(batch, n, dev_out(o), call.s, &st, nullptr) != hipSuccess)
+    return FST_OOM;
+  st.launches += p.launches;
+  t_last_stats = st;
+  call.drain.done = true;  // (run_nbest_batch synchronised the stream)
   return FST_OK;
 }
 

@@ -1,7 +1,8 @@
 // batch_lhs.cpp -- host batches of general lhs (lattices, confusion networks) and the lattice
 // batch: the staging of a shard's items into one block (stage_lhs_items), the shard steps on it
-// (1-best, pipelines on a general first stage, shortest path, connect), the lattice arena with
-// its reruns, the trim driver, the two lattice shard steps, and the lattice sink of run_sharded.
+// (1-best, pipelines on a general first stage, shortest path, n-best, connect), the lattice arena
+// with its reruns, the trim driver, the two lattice shard steps, and the lattice sink of
+// run_sharded.
 // run_arena, run_sharded itself and the chain stages: batch_sharded.cpp.
 #include <cmath>
 
@@ -128,11 +129,15 @@ FstError run_lhs_shard(Shard& S, FrozenFst& b, const FstLhsBatch& L, uint32_t n,
       &h, &S.keep);
 }
 
-// One shard of fst_shortest_path_lhs_batch: the staged items through DeviceEngine::run_sp_batch,
-// which reads the staged block in place.  An OK path has at most num_states - 1 arcs (a longer
-// back-pointer walk is a cycle), so an arena of the shard's states is never too small: no
-// OUTPUT_FULL, no rerun.
-FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n) {
+namespace {
+// The shard step of the two entries that reduce the staged items to paths with no compose: `run`
+// is an engine call that reads the staged block in place and synchronises the stream; `per`
+// strings per item.  A path of theirs has fewer arcs than its item has states (a longer
+// back-pointer walk is a cycle; an n-best item is acyclic), so an arena of `per` times the
+// shard's states is never too small: no OUTPUT_FULL, no rerun.
+template <class Run>
+FstError staged_paths_shard(Shard& S, const FstLhsBatch& L, uint32_t per, const char* failed,
+                            const Run& run) {
   const int dev = S.E->dev();
   if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
   const hipStream_t stream = S.E.stream();
@@ -141,22 +146,42 @@ FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n) {
   // every return drains the stream before the staged blocks and the arena go back to their pools
   StreamDrain drain{{stream}};
   if (FstError e = stage_lhs_items(S, nullptr, L, stream, &st); e != FST_OK) return e;
-  auto out = std::make_unique<DevOut>(num, std::max<uint64_t>(st.b.total_states, 1));
+  auto out = std::make_unique<DevOut>(num * per, std::max<uint64_t>(st.b.total_states * per, 1));
   if (!out->ok()) return FST_OOM;
   if (t_prof) t_prof->lap(1);
   LaunchStats ls;
-  const hipError_t err = S.E->run_sp_batch(st.b, n, out->v, stream, &ls, nullptr);
+  const hipError_t err = run(st.b, out->v, stream, &ls);
   if (t_prof) {
     t_prof->lap(2);
     ++t_prof->runs;
   }
   if (err != hipSuccess) {
-    std::fprintf(stderr, "[libfst_amd] lattice shortest path failed: %s\n", hipGetErrorString(err));
+    std::fprintf(stderr, "[libfst_amd] %s failed: %s\n", failed, hipGetErrorString(err));
     return FST_OOM;
   }
   t_last_stats = ls;
   S.keep = std::move(out);
-  return FST_OK;  // (the drain: run_sp_batch synchronised, nothing is left to wait for)
+  return FST_OK;  // (the drain: `run` synchronised, nothing is left to wait for)
+}
+}  // namespace
+
+// One shard of fst_shortest_path_lhs_batch: the staged items through DeviceEngine::run_sp_batch.
+FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n) {
+  return staged_paths_shard(
+      S, L, 1, "lattice shortest path",
+      [&](const LhsBatchDev& b, const BatchOutDev& v, hipStream_t stream, LaunchStats* ls) {
+        return S.E->run_sp_batch(b, n, v, stream, ls, nullptr);
+      });
+}
+
+// One shard of fst_nbest_lhs_batch: the same through DeviceEngine::run_nbest_batch, n strings
+// per item (run_sharded's `per`).
+FstError run_nbest_shard(Shard& S, const FstLhsBatch& L, uint32_t n) {
+  return staged_paths_shard(
+      S, L, n, "lattice n-best",
+      [&](const LhsBatchDev& b, const BatchOutDev& v, hipStream_t stream, LaunchStats* ls) {
+        return S.E->run_nbest_batch(b, n, v, stream, ls, nullptr);
+      });
 }
 
 // ---- Lattice shards ---------------------------------------------------------------------

@@ -76,7 +76,7 @@ uint32_t rebase_offsets(const uint64_t* offsets, uint32_t num, std::vector<uint6
 }
 
 FstError shard_compact(Shard& S) {
-  const uint32_t num = S.s1 - S.s0;
+  const uint32_t num = (S.s1 - S.s0) * S.per;
   const hipStream_t stream = S.E.stream();
   const DevOut& o = *S.keep;
   unsigned long long used = 0;
@@ -101,10 +101,10 @@ FstError shard_compact(Shard& S) {
 // D2H of a compacted shard into the (pinned) result, asynchronously on `stream`: no
 // synchronisation and no offset fix-up (the pipelined host batch does both once at the end).
 bool shard_download_async(Shard& S, FstBatchResult* out, uint64_t arc_base, hipStream_t stream) {
-  const uint32_t num = S.s1 - S.s0;
-  return d2h(out->status + S.s0, S.st->p, num * 4ull, stream) &&
-         d2h(out->final_weights + S.s0, S.fin->p, num * 8ull, stream) &&
-         d2h(out->path_offsets + S.s0, S.off->p, num * 8ull, stream) &&
+  const uint32_t first = S.s0 * S.per, num = (S.s1 - S.s0) * S.per;
+  return d2h(out->status + first, S.st->p, num * 4ull, stream) &&
+         d2h(out->final_weights + first, S.fin->p, num * 8ull, stream) &&
+         d2h(out->path_offsets + first, S.off->p, num * 8ull, stream) &&
          d2h(out->ilabels + arc_base, S.il->p, S.tot * 4, stream) &&
          d2h(out->olabels + arc_base, S.ol->p, S.tot * 4, stream) &&
          d2h(out->weights + arc_base, S.w->p, S.tot * 8, stream);
@@ -117,7 +117,7 @@ FstError shard_download(Shard& S, FstBatchResult* out, uint64_t arc_base) {
   if (!shard_download_async(S, out, arc_base, stream) || hipStreamSynchronize(stream) != hipSuccess)
     return FST_OOM;
   if (arc_base)
-    for (uint32_t i = S.s0; i < S.s1; ++i) out->path_offsets[i] += arc_base;
+    for (uint32_t i = S.s0 * S.per; i < S.s1 * S.per; ++i) out->path_offsets[i] += arc_base;
   return FST_OK;
 }
 
@@ -497,14 +497,22 @@ FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num
 
 FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
                      const std::vector<double>& cost, const ShardCompute& compute,
-                     FstBatchResult* out) {
+                     FstBatchResult* out, uint32_t per) {
+  const uint32_t strings = num * per;
   const ShardSink sink{shard_compact,
-                       [=](uint64_t tot, uint64_t) { return alloc_result(out, num, tot); },
+                       [=](uint64_t tot, uint64_t) { return alloc_result(out, strings, tot); },
                        [=](Shard& S, uint64_t base, uint64_t) {
                          return shard_download(S, out, base);
                        },
-                       [=](uint64_t tot, uint64_t) { out->path_offsets[num] = tot; }};
-  return run_sharded(devices, nsh, num, cost, compute, sink);
+                       [=](uint64_t tot, uint64_t) { out->path_offsets[strings] = tot; }};
+  if (per == 1) return run_sharded(devices, nsh, num, cost, compute, sink);
+  return run_sharded(
+      devices, nsh, num, cost,
+      [&](Shard& S) {
+        S.per = per;
+        return compute(S);
+      },
+      sink);
 }
 
 

@@ -330,6 +330,34 @@ struct LatSpDev {
   uint32_t n_best;
   unsigned long long wd_ticks;
 };
+// The lattice n-best's inputs and workspace (kernels/lattice_nbest.hpp): the n
+// best distinct paths of every item of an lhs batch, the batch's CSR read in place.
+constexpr uint32_t kNbestMax = 16;  // FST_NBEST_MAX
+enum : uint32_t { kNbCtrList = 0, kNbCtrLds = 1, kNbCtrHbm = 2, kNbCtrWords = 4 };
+struct LatNbestDev {
+  const struct LhsDesc* desc;  // [num]
+  const uint32_t* state_off;   // the batch's arrays, as GraphInput holds them for a batch
+  const double* final_w;
+  const uint32_t* arc_next;
+  const uint32_t* arc_il;
+  const uint32_t* arc_ol;
+  const double* arc_w;
+  // the HBM tier's tables (null while the LDS tier runs), an item's slice at its bases
+  unsigned long long* eg;      // [states * n] list entries: the cost ...
+  unsigned long long* ear;     // [states * n]     ... and (last arc << 32) | rank of the rest
+  uint32_t* depth;             // [states] five words per state
+  uint32_t* roff;
+  uint32_t* cnt;
+  uint32_t* lvl;
+  uint32_t* order;
+  uint32_t* rarc;              // [arcs] two words per arc
+  uint32_t* asrc;
+  uint32_t* list;              // [num] items the LDS tier handed on
+  uint32_t* ctr;               // [kNbCtrWords] the list's length, items finished per tier
+  uint32_t n_best;
+  uint32_t lds_budget;         // bytes of dynamic LDS per workgroup of the LDS tier
+  unsigned long long wd_ticks;
+};
 
 // Chain inputs (batch API) or one general lhs FST (single-call C ABI).
 struct ChainInput {
@@ -543,6 +571,11 @@ hipError_t launch_align_compose(uint32_t num, const uint64_t* outer_off, const u
                                 const uint32_t* in_begin, const uint32_t* in_end,
                                 const uint32_t* n1, uint32_t* out_begin, uint32_t* out_end,
                                 uint64_t cap, uint32_t grid, hipStream_t stream);
+// ---- lattice n-best (lattice_nbest.hip, kernels/lattice_nbest.hpp) ----
+hipError_t launch_nbest_lds(const LatNbestDev& p, uint32_t count, const BatchOutDev& out,
+                            uint32_t grid, hipStream_t stream);
+hipError_t launch_nbest_hbm(const LatNbestDev& p, const BatchOutDev& out, uint32_t grid,
+                            hipStream_t stream);
 // On-device preparation of a device-resident batch (kernels/lhs_prepare.hpp; lhs_batch.hip
 // holds the instances).  In: the caller's arrays in FstLhsBatch's layout, all device memory,
 // and their two extents as the host read them.  Out: descriptors, local arc offsets
@@ -713,6 +746,16 @@ class DeviceEngine {
   // cursor at what the batch needs.  Synchronises `stream`.
   hipError_t run_sp_batch(const LhsBatchDev& b, uint32_t n, const BatchOutDev& out,
                           hipStream_t stream, LaunchStats* stats, LhsRoute* route);
+  // The n best distinct paths of every item of an lhs batch (fst_nbest_lhs_batch; kernels/
+  // lattice_nbest.hpp): item i's k-th best is string i * n + k of `out`, which has room for
+  // num * n strings; 1 <= n <= kNbestMax.  The LDS tier (one wave per item, a budget of
+  // 4 KiB + n KiB of LDS per workgroup, or FSTAMD_NBEST_LDS bytes; 0: no item fits) hands the
+  // items whose tables do not fit to the HBM tier, whose workspace b's extents size (it is
+  // allocated only when an item needs it).  Strings the arena cannot hold end OUTPUT_FULL, the
+  // cursor at what the batch needs.  route: t[0..1] = items the LDS / HBM tier finished.
+  // Synchronises `stream`.
+  hipError_t run_nbest_batch(const LhsBatchDev& b, uint32_t n, const BatchOutDev& out,
+                             hipStream_t stream, LaunchStats* stats, LhsRoute* route);
   // fst_compose_frozen: the whole lattice of one general lhs (kernels/eager_bfs.hpp), on
   // `stream` (synchronised: the lattice is downloaded).
   hipError_t compose_lattice(const DeviceFst& rhs, const GraphInput& lhs, HostLattice* lat,

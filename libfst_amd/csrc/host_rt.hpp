@@ -192,6 +192,9 @@ struct AlignMap {
 struct Shard {
   int dev = 0;
   uint32_t s0 = 0, s1 = 0;
+  // result strings per item: 1, or fst_nbest_lhs_batch's n (run_sharded's `per`); the label
+  // gather then moves strings [s0 * per, s1 * per)
+  uint32_t per = 1;
   DeviceEngine::Lease E;
   std::unique_ptr<DevOut> keep;
   std::unique_ptr<LatShard> lat;  // lattice entries (keep: the statuses)
@@ -257,10 +260,11 @@ bool alloc_aligned_text_result(FstAlignedTextResult* out, uint32_t num, uint64_t
 FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
                      const std::vector<double>& cost, const ShardCompute& compute,
                      const ShardSink& sink);
-// ... into a label result: compact_paths on the device, then the arc arrays by DMA.
+// ... into a label result: compact_paths on the device, then the arc arrays by DMA.  `per`:
+// result strings per item (the result has num * per, Shard::per is set before `compute` runs).
 FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
                      const std::vector<double>& cost, const ShardCompute& compute,
-                     FstBatchResult* out);
+                     FstBatchResult* out, uint32_t per = 1);
 // ... into a text result (fst_normalize_text_batch): text_count / text_write on the device.
 FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,
                      const std::vector<double>& cost, const ShardCompute& compute,
@@ -301,6 +305,9 @@ FstError run_lhs_pipeline_shard(Shard& S, const Stages& fs, const FstLhsBatch& L
 // fst_shortest_path_lhs_batch's shard: the items staged the same way, then fst_shortest_path of
 // each (DeviceEngine::run_sp_batch) into a path arena of the shard's states; S.keep = the paths.
 FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n);
+// fst_nbest_lhs_batch's shard: the same staging, then DeviceEngine::run_nbest_batch into n
+// strings per item and a path arena of n times the shard's states; S.keep = the paths.
+FstError run_nbest_shard(Shard& S, const FstLhsBatch& L, uint32_t n);
 // fst_connect_lhs_batch's shard: the items staged the same way, then trimmed.
 FstError run_connect_shard(Shard& S, const FstLhsBatch& L);
 // The compute steps of a lattice shard: chains from the caller's labels, or general lhs staged

@@ -90,6 +90,7 @@ class FstDeviceBatch(C.Structure):
 
 FST_LATTICE_PROJECT_OUTPUT = 1
 FST_LATTICE_CONNECT = 4  # (bit 1 is not assigned)
+FST_NBEST_MAX = 16
 
 
 class FstLatticeBatch(C.Structure):
@@ -177,6 +178,12 @@ SIGNATURES = {
     "fst_shortest_path_lhs_batch": (
         C.c_int, [C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstBatchResult)]),
+    "fst_nbest_lhs_batch": (
+        C.c_int, [C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstBatchResult)]),
+    "fst_device_nbest_lhs": (
+        C.c_int, [C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstDeviceBatch), _P]),
     "fst_device_compose_frozen": (
         C.c_int, [_u64, _P, _P, _u32, _u32, _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceLattices), C.POINTER(_u64), _P]),
@@ -644,6 +651,20 @@ def shortest_path_lhs_batch(lhs: LhsBatch, n: int = 1, device: int = -1, devices
     if rc != FST_OK:
         raise RuntimeError(f"fst_shortest_path_lhs_batch failed: {rc}")
     return _take_result(res, len(lhs))
+
+
+def nbest_lhs_batch(lhs: LhsBatch, n: int, device: int = -1, devices=None,
+                    shards: int = 0) -> BatchResult:
+    """The n best distinct paths of every item of an lhs batch of acyclic items
+    (fst_nbest_lhs_batch; the order is defined in fst_batch.h): a BatchResult of len(lhs) * n
+    strings, item i's k-th best at i * n + k, EMPTY past the item's last path."""
+    opts = batch_options(device, FST_SEM_LAZY, devices, shards)
+    res = FstBatchResult()
+    cs = lhs.c_struct()
+    rc = lib().fst_nbest_lhs_batch(C.byref(cs), n, C.byref(opts), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_nbest_lhs_batch failed: {rc}")
+    return _take_result(res, len(lhs) * n)
 
 
 def pipeline_lhs_batch(stages, lhs: LhsBatch, n: int = 1, semantics: int = FST_SEM_LAZY,
