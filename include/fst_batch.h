@@ -425,6 +425,45 @@ FstError fst_nbest_lhs_batch(const FstLhsBatch* lhs, uint32_t n, const FstBatchO
 FstError fst_device_nbest_lhs(const FstLhsBatch* d_lhs, uint32_t n, const FstBatchOptions* opts,
                               const FstDeviceBatch* out, void* stream);
 
+/* The n best paths WITH DISTINCT OUTPUT TEXT of every item of an lhs batch, for acyclic items:
+ * what OpenFst and Pynini callers know as ShortestPath(nshortest = n, unique = true), without a
+ * determinisation.  Everything fst_nbest_lhs_batch says about arguments, validation (the same
+ * FST_INVALID_ARG cases, n <= FST_NBEST_MAX, num_fsts * n < 2^32), the result layout (string
+ * i * n + k), the item statuses and their order, sharding and the empty batch holds here
+ * unchanged; the plain entries and their results do not change.
+ * Definition.
+ *   The OUTPUT TEXT of a path is the sequence of its non-epsilon olabels (olabel != 0), as u32
+ *   labels; a label above 256 is a label like any other here.
+ *   Take all complete paths of the item in the order fst_nbest_lhs_batch defines: total, then
+ *   final state t, then the prefix order at t.  That order does not depend on n.
+ *   Drop every path whose output text equals that of an earlier path.
+ *   String i * n + k is the k-th path that is left, FST_PATH_OK; its arcs, weights and final
+ *   weight are copied as the plain entry copies them.  An item with m < n distinct texts leaves
+ *   the rest FST_PATH_EMPTY.
+ * So n = 1 equals fst_nbest_lhs_batch at n = 1 byte for byte, an item whose complete paths all
+ * print different texts gives the plain entry's result, and the OK strings of one item have
+ * pairwise different output texts.
+ * How it is computed: Eu(t), the at most n least prefixes ending in t with pairwise different
+ * output texts, each (g, a, r) with r the rank of the rest in Eu(src(a)).  Among the candidates
+ * (fl(Eu(src(a))[r].g + w(a)), a, r) with the same text only the least in (g, a, r) order is
+ * kept.  Nothing is lost: if n prefixes with other texts precede p at s, their extensions by
+ * the same suffix are n complete paths with n other texts, none after p's; the order is strict
+ * under extension by one arc, because equal g falls back to the order of the rests.  The final
+ * selection applies the same rule across final states: candidates in (total, t, r) order, a
+ * candidate whose text was already chosen is passed over.  Texts are compared label by label;
+ * a 64-bit hash per prefix only spares comparisons.
+ * fst_last_launch_stats reports engine 14. */
+FstError fst_nbest_unique_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
+                                    const FstBatchOptions* opts, FstBatchResult* out);
+
+/* Device-resident, exactly as fst_device_nbest_lhs: trusted extents, the prepare kernel (an item
+ * it refuses is FST_PATH_UNSUPPORTED), the caller's arena with FST_PATH_OUTPUT_FULL and
+ * *arc_cursor at what the batch needs, the call SYNCHRONISES `stream`.  The result chains into
+ * fst_device_emit_text: text in, n distinct readings out.  Engine 14. */
+FstError fst_device_nbest_unique_lhs(const FstLhsBatch* d_lhs, uint32_t n,
+                                     const FstBatchOptions* opts, const FstDeviceBatch* out,
+                                     void* stream);
+
 /* The device-resident form, chains in and lattices out, so that a cascade never leaves the
  * device.  Every pointer in `out` is device memory on opts->device, in FstLhsBatch's layout: a
  * host-side FstLhsBatch holding those pointers goes straight into
@@ -633,7 +672,10 @@ typedef struct {
                                         frontier and heap-replay tiers behind it),
                                    13 = fst_nbest_lhs_batch and fst_device_nbest_lhs (one wave
                                         per lattice with its tables in LDS, a workgroup per
-                                        lattice with them in HBM behind it) */
+                                        lattice with them in HBM behind it),
+                                   14 = fst_nbest_unique_lhs_batch and
+                                        fst_device_nbest_unique_lhs (engine 13's two tiers with
+                                        a text hash per list entry) */
     uint32_t grid;              /* workgroups of the dominant kernel */
 } FstLaunchStats;
 FstError fst_last_launch_stats(FstLaunchStats* out);

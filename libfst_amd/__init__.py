@@ -16,4 +16,5 @@ from .fst import (  # noqa: F401
     LatticeBatch, compose_frozen_batch, compose_frozen_lhs_batch,
     FST_LATTICE_CONNECT, connect_lhs_batch, shortest_path_lhs_batch,
     AlignedTextResult, FstAlignedTextResult, batch_result_to_aligned_text,
-    normalize_text_aligned_batch, FST_NBEST_MAX, nbest_lhs_batch)
+    normalize_text_aligned_batch, FST_NBEST_MAX, nbest_lhs_batch,
+    nbest_unique_lhs_batch)

@@ -521,16 +521,28 @@ FstError fst_shortest_path_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
 
 // The n best distinct paths of every item of an lhs batch: staged as above, n strings per item
 // (run_nbest_shard; the gather moves a shard's items [s0, s1) as strings [s0 * n, s1 * n)).
-FstError fst_nbest_lhs_batch(const FstLhsBatch* lhs, uint32_t n, const FstBatchOptions* opts,
-                             FstBatchResult* out) {
+// unique: the n best paths of distinct output texts, the same frame.
+static FstError nbest_lhs_entry(const FstLhsBatch* lhs, uint32_t n, bool unique,
+                                const FstBatchOptions* opts, FstBatchResult* out,
+                                const char* name) {
   if (!out) return FST_INVALID_ARG;
   std::memset(out, 0, sizeof(*out));
   // (n and the slot count before the validator: it reads num_fsts entries of the arrays)
   if (!lhs || !nbest_slots_ok(lhs->num_fsts, n) || !lhs_batch_valid(lhs) || !flags_ok(opts))
     return FST_INVALID_ARG;
   return lhs_sharded(
-      lhs, opts, true, out, "fst_nbest_lhs_batch", fst_batch_result_free,
-      [&](Shard& S, const BatchCall&) { return run_nbest_shard(S, *lhs, n); }, n);
+      lhs, opts, true, out, name, fst_batch_result_free,
+      [&](Shard& S, const BatchCall&) { return run_nbest_shard(S, *lhs, n, unique); }, n);
+}
+
+FstError fst_nbest_lhs_batch(const FstLhsBatch* lhs, uint32_t n, const FstBatchOptions* opts,
+                             FstBatchResult* out) {
+  return nbest_lhs_entry(lhs, n, false, opts, out, "fst_nbest_lhs_batch");
+}
+
+FstError fst_nbest_unique_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
+                                    const FstBatchOptions* opts, FstBatchResult* out) {
+  return nbest_lhs_entry(lhs, n, true, opts, out, "fst_nbest_unique_lhs_batch");
 }
 
 void fst_lattice_batch_free(FstLatticeBatch* r) {
@@ -652,9 +664,11 @@ FstError fst_device_shortest_path_lhs(const FstLhsBatch* d_lhs, uint32_t n,
 }
 
 // The n best paths of a device-resident lhs batch: prepared like the shortest path's, then
-// DeviceEngine::run_nbest_batch into the caller's arena, n strings per item.
-FstError fst_device_nbest_lhs(const FstLhsBatch* d_lhs, uint32_t n, const FstBatchOptions* opts,
-                              const FstDeviceBatch* o, void* stream) {
+// DeviceEngine::run_nbest_batch into the caller's arena, n strings per item.  unique: the n best
+// paths of distinct output texts.
+static FstError device_nbest_entry(const FstLhsBatch* d_lhs, uint32_t n, bool unique,
+                                   const FstBatchOptions* opts, const FstDeviceBatch* o,
+                                   void* stream) {
   if (!device_lhs_args_ok(d_lhs) || !device_batch_out_ok(o, d_lhs->num_fsts) || !flags_ok(opts) ||
       !nbest_slots_ok(d_lhs->num_fsts, n))
     return FST_INVALID_ARG;
@@ -664,12 +678,23 @@ FstError fst_device_nbest_lhs(const FstLhsBatch* d_lhs, uint32_t n, const FstBat
   LhsPrepared p;
   if (FstError e = device_lhs_prepare(call, d_lhs, &batch, &p); e != FST_OK) return e;
   LaunchStats st;
-  if (call.E->run_nbest_batch(batch, n, dev_out(o), call.s, &st, nullptr) != hipSuccess)
+  if (call.E->run_nbest_batch(batch, n, unique, dev_out(o), call.s, &st, nullptr) != hipSuccess)
     return FST_OOM;
   st.launches += p.launches;
   t_last_stats = st;
   call.drain.done = true;  // (run_nbest_batch synchronised the stream)
   return FST_OK;
+}
+
+FstError fst_device_nbest_lhs(const FstLhsBatch* d_lhs, uint32_t n, const FstBatchOptions* opts,
+                              const FstDeviceBatch* o, void* stream) {
+  return device_nbest_entry(d_lhs, n, false, opts, o, stream);
+}
+
+FstError fst_device_nbest_unique_lhs(const FstLhsBatch* d_lhs, uint32_t n,
+                                     const FstBatchOptions* opts, const FstDeviceBatch* o,
+                                     void* stream) {
+  return device_nbest_entry(d_lhs, n, true, opts, o, stream);
 }
 
 FstError fst_device_project_output(const FstDeviceBatch* o, uint32_t num_strings,

@@ -174,13 +174,13 @@ FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n) {
       });
 }
 
-// One shard of fst_nbest_lhs_batch: the same through DeviceEngine::run_nbest_batch, n strings
-// per item (run_sharded's `per`).
-FstError run_nbest_shard(Shard& S, const FstLhsBatch& L, uint32_t n) {
+// One shard of fst_nbest_lhs_batch, with `unique` of fst_nbest_unique_lhs_batch: the same
+// through DeviceEngine::run_nbest_batch, n strings per item (run_sharded's `per`).
+FstError run_nbest_shard(Shard& S, const FstLhsBatch& L, uint32_t n, bool unique) {
   return staged_paths_shard(
-      S, L, n, "lattice n-best",
+      S, L, n, unique ? "lattice n-best (unique)" : "lattice n-best",
       [&](const LhsBatchDev& b, const BatchOutDev& v, hipStream_t stream, LaunchStats* ls) {
-        return S.E->run_nbest_batch(b, n, v, stream, ls, nullptr);
+        return S.E->run_nbest_batch(b, n, unique, v, stream, ls, nullptr);
       });
 }
 

@@ -3129,15 +3129,16 @@ hipError_t DeviceEngine::run_sp_batch(const LhsBatchDev& b, uint32_t n, const Ba
 
 // ---- lattice n-best (lattice_nbest.hip holds the kernels) --------------------------------
 
-hipError_t DeviceEngine::run_nbest_batch(const LhsBatchDev& b, uint32_t n, const BatchOutDev& out,
-                                         hipStream_t stream, LaunchStats* stats, LhsRoute* route) {
+hipError_t DeviceEngine::run_nbest_batch(const LhsBatchDev& b, uint32_t n, bool unique,
+                                         const BatchOutDev& out, hipStream_t stream,
+                                         LaunchStats* stats, LhsRoute* route) {
   HIP_TRY(hipSetDevice(dev_));
   const GraphInput& lhs = b.lhs;
   const uint32_t num = b.in.num_strings;
   if (n == 0 || n > kNbestMax || (uint64_t)num * n >= (1ull << 32)) return hipErrorInvalidValue;
   HIP_TRY(hipMemsetAsync(out.cursor, 0, sizeof(unsigned long long), stream));
   if (stats) {
-    stats->engine = 13;
+    stats->engine = unique ? 14 : 13;
     stats->grid = 0;
     stats->launches = 0;
   }
@@ -3145,7 +3146,8 @@ hipError_t DeviceEngine::run_nbest_batch(const LhsBatchDev& b, uint32_t n, const
   // The LDS tier's budget per workgroup (one wave): 4 KiB + n KiB, the best of a sweep from 8 to
   // 60 KiB on the tagger stand-in's lattices at n = 1, 4, 8 and 16 (a larger one
   // costs residency faster than it saves HBM-tier items).  Tests move it: FSTAMD_NBEST_LDS
-  // bytes, 0 sends every item to the HBM tier.
+  // bytes, 0 sends every item to the HBM tier.  The unique instances keep the rule: their 24 B
+  // per list entry send items to the HBM tier earlier (not swept: DESIGN.md §7j).
   uint32_t budget = 4096 + 1024 * n;
   if (const char* e = std::getenv("FSTAMD_NBEST_LDS"))
     if (*e) budget = (uint32_t)std::min<unsigned long long>(std::strtoull(e, nullptr, 10), 61440);
@@ -3166,6 +3168,10 @@ hipError_t DeviceEngine::run_nbest_batch(const LhsBatchDev& b, uint32_t n, const
   p.n_best = n;
   p.lds_budget = budget;
   p.wd_ticks = watchdog_ticks();
+  // (tests: a hex mask on every text hash; the result is the same under any, 0 included)
+  p.hash_mask = ~0ull;
+  if (const char* e = std::getenv("FSTAMD_NBEST_HASH_MASK"))
+    if (*e) p.hash_mask = std::strtoull(e, nullptr, 16);
   // every string starts as INTERNAL: one no kernel finished can never read as a result
   HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out.status, kPathInternal, (size_t)num * n, stream));
   HIP_TRY(hipMemsetAsync(p.ctr, 0, kNbCtrWords * 4, stream));
@@ -3174,19 +3180,22 @@ hipError_t DeviceEngine::run_nbest_batch(const LhsBatchDev& b, uint32_t n, const
   HIP_TRY(timed(stats, stream, [&]() -> hipError_t {
     const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(32, 163840 / (budget + 512)));
     grid_max = std::max<uint32_t>(1, std::min({num, cus * per_cu, cap}));
-    HIP_TRY(launch_nbest_lds(p, num, out, grid_max, stream));
+    HIP_TRY(launch_nbest_lds(p, unique, num, out, grid_max, stream));
     ++launches;
     HIP_TRY(copy_sync(ctr, p.ctr, sizeof(ctr), hipMemcpyDeviceToHost, stream));
     const uint32_t handed = ctr[kNbCtrList];
     if (handed > num) return hipErrorUnknown;  // (the list holds an item at most once)
     if (handed == 0) return hipSuccess;
-    // the HBM tier's tables in one block: 16 B per list entry, then the state and arc words
+    // the HBM tier's tables in one block: 16 B per list entry (24 B with the text hashes of a
+    // unique call), then the state and arc words
     const size_t ns = (size_t)b.total_states + 4, na = (size_t)b.total_arcs + 4;
-    uint8_t* w = (uint8_t*)scratch(kNbWork, 16 * ns * n + 4 * (5 * ns + 2 * na));
+    const size_t words = unique ? 3 : 2;
+    uint8_t* w = (uint8_t*)scratch(kNbWork, 8 * words * ns * n + 4 * (5 * ns + 2 * na));
     if (!w) return hipErrorOutOfMemory;
     p.eg = (unsigned long long*)w;
     p.ear = p.eg + ns * n;
-    p.depth = (uint32_t*)(p.ear + ns * n);
+    p.eh = unique ? p.ear + ns * n : nullptr;
+    p.depth = (uint32_t*)(p.eg + words * ns * n);
     p.roff = p.depth + ns;
     p.cnt = p.roff + ns;
     p.lvl = p.cnt + ns;
@@ -3194,7 +3203,7 @@ hipError_t DeviceEngine::run_nbest_batch(const LhsBatchDev& b, uint32_t n, const
     p.rarc = p.order + ns;
     p.asrc = p.rarc + na;
     const uint32_t g = std::max<uint32_t>(1, std::min({handed, cus * 8, cap}));
-    HIP_TRY(launch_nbest_hbm(p, out, g, stream));
+    HIP_TRY(launch_nbest_hbm(p, unique, out, g, stream));
     grid_max = std::max(grid_max, g);
     ++launches;
     return copy_sync(ctr, p.ctr, sizeof(ctr), hipMemcpyDeviceToHost, stream);
@@ -3207,8 +3216,9 @@ hipError_t DeviceEngine::run_nbest_batch(const LhsBatchDev& b, uint32_t n, const
     stats->launches = launches;
   }
   if (std::getenv("FSTAMD_ROUTE_LOG"))
-    std::fprintf(stderr, "[libfst_amd route] lattice nbest: items %u | lds %u hbm %u | %.3f ms\n",
-                 num, ctr[kNbCtrLds], ctr[kNbCtrHbm], stats ? stats->kernel_ms : 0.0);
+    std::fprintf(stderr, "[libfst_amd route] lattice %s: items %u | lds %u hbm %u | %.3f ms\n",
+                 unique ? "nbest-unique" : "nbest", num, ctr[kNbCtrLds], ctr[kNbCtrHbm],
+                 stats ? stats->kernel_ms : 0.0);
   if (route) {
     *route = LhsRoute();
     route->t[0] = ctr[kNbCtrLds];

@@ -357,6 +357,9 @@ struct LatNbestDev {
   uint32_t n_best;
   uint32_t lds_budget;         // bytes of dynamic LDS per workgroup of the LDS tier
   unsigned long long wd_ticks;
+  // the unique instances alone (distinct output texts)
+  unsigned long long* eh;      // [states * n] the HBM tier's text hashes, beside eg and ear
+  unsigned long long hash_mask;  // ANDed onto every hash (FSTAMD_NBEST_HASH_MASK; all ones)
 };
 
 // Chain inputs (batch API) or one general lhs FST (single-call C ABI).
@@ -572,10 +575,11 @@ hipError_t launch_align_compose(uint32_t num, const uint64_t* outer_off, const u
                                 const uint32_t* n1, uint32_t* out_begin, uint32_t* out_end,
                                 uint64_t cap, uint32_t grid, hipStream_t stream);
 // ---- lattice n-best (lattice_nbest.hip, kernels/lattice_nbest.hpp) ----
-hipError_t launch_nbest_lds(const LatNbestDev& p, uint32_t count, const BatchOutDev& out,
+// (unique: the instances that keep one path per output text)
+hipError_t launch_nbest_lds(const LatNbestDev& p, bool unique, uint32_t count,
+                            const BatchOutDev& out, uint32_t grid, hipStream_t stream);
+hipError_t launch_nbest_hbm(const LatNbestDev& p, bool unique, const BatchOutDev& out,
                             uint32_t grid, hipStream_t stream);
-hipError_t launch_nbest_hbm(const LatNbestDev& p, const BatchOutDev& out, uint32_t grid,
-                            hipStream_t stream);
 // On-device preparation of a device-resident batch (kernels/lhs_prepare.hpp; lhs_batch.hip
 // holds the instances).  In: the caller's arrays in FstLhsBatch's layout, all device memory,
 // and their two extents as the host read them.  Out: descriptors, local arc offsets
@@ -753,9 +757,13 @@ class DeviceEngine {
   // items whose tables do not fit to the HBM tier, whose workspace b's extents size (it is
   // allocated only when an item needs it).  Strings the arena cannot hold end OUTPUT_FULL, the
   // cursor at what the batch needs.  route: t[0..1] = items the LDS / HBM tier finished.
+  // unique (fst_nbest_unique_lhs_batch, engine 14): the n best paths with pairwise different
+  // output texts, by the instances that carry a text hash per list entry; their tables take
+  // 24 B per entry against the same budget, and the workspace holds the hashes too.
   // Synchronises `stream`.
-  hipError_t run_nbest_batch(const LhsBatchDev& b, uint32_t n, const BatchOutDev& out,
-                             hipStream_t stream, LaunchStats* stats, LhsRoute* route);
+  hipError_t run_nbest_batch(const LhsBatchDev& b, uint32_t n, bool unique,
+                             const BatchOutDev& out, hipStream_t stream, LaunchStats* stats,
+                             LhsRoute* route);
   // fst_compose_frozen: the whole lattice of one general lhs (kernels/eager_bfs.hpp), on
   // `stream` (synchronised: the lattice is downloaded).
   hipError_t compose_lattice(const DeviceFst& rhs, const GraphInput& lhs, HostLattice* lat,

@@ -307,7 +307,8 @@ FstError run_lhs_pipeline_shard(Shard& S, const Stages& fs, const FstLhsBatch& L
 FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n);
 // fst_nbest_lhs_batch's shard: the same staging, then DeviceEngine::run_nbest_batch into n
 // strings per item and a path arena of n times the shard's states; S.keep = the paths.
-FstError run_nbest_shard(Shard& S, const FstLhsBatch& L, uint32_t n);
+// unique: fst_nbest_unique_lhs_batch's (one path per output text).
+FstError run_nbest_shard(Shard& S, const FstLhsBatch& L, uint32_t n, bool unique);
 // fst_connect_lhs_batch's shard: the items staged the same way, then trimmed.
 FstError run_connect_shard(Shard& S, const FstLhsBatch& L);
 // The compute steps of a lattice shard: chains from the caller's labels, or general lhs staged

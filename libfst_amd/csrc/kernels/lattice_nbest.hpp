@@ -20,6 +20,14 @@
 // with ld_agent as the frontier tier of lattice_sp.hpp reads its own.
 // Every loop is bounded: the depth rounds by the state count, the levels likewise, both by the
 // deadline; walks by the state count.  Every index read from a table is checked before use.
+//
+// kUnique (fst_nbest_unique_lhs_batch / fst_device_nbest_unique_lhs): the n best
+// paths with pairwise different OUTPUT TEXTS (the non-epsilon olabels).  A third word per list
+// entry, eh, holds a 64-bit hash of the prefix's text; a list keeps per text only its least
+// prefix (nb_pull), the selection passes over a winner whose text was chosen before.  Different
+// hashes mean different texts; equal hashes are confirmed label by label (nb_same_text), so the
+// result does not depend on the hash (FSTAMD_NBEST_HASH_MASK).  The tables are then 24 B per
+// list entry.  The plain instances hold none of this.
 #pragma once
 #include "eager_bfs.hpp"
 
@@ -64,6 +72,7 @@ __device__ __forceinline__ NbItem nb_item(const LatNbestDev& p, uint32_t si) {
 struct NbTables {
   unsigned long long* eg;   // [S * n] the cost of list entry r of state t at t * n + r
   unsigned long long* ear;  // [S * n] (last arc << 32) | rank of the rest in E(src)
+  unsigned long long* eh;   // [S * n] kUnique: the hash of the prefix's output text
   uint32_t* depth;          // [S] depth + 1; 0: not reached
   uint32_t* roff;           // [S] in-arc counts, then offsets, after the fill the ends
   uint32_t* cnt;            // [S] entries in E(t)
@@ -79,6 +88,10 @@ struct NbShared {
   uint32_t scan[kNbWG / 64];
   unsigned long long red[kNbWG / 64];
   unsigned long long sel[kNbestMax];
+};
+// kUnique: the hashes of the texts chosen so far, beside their (t, r) in sel.
+struct NbSharedUnique : NbShared {
+  unsigned long long selh[kNbestMax];
 };
 
 template <bool kLds, class T>
@@ -167,15 +180,74 @@ __device__ __forceinline__ bool nb_less(double g, unsigned long long ar, double 
   return g < pg || (g == pg && ar < par);
 }
 
-// E(t) of one state, by one lane: see the file comment.
+// ---- kUnique: the output text of a prefix ---------------------------------------------------
+constexpr unsigned long long kNbHashSeed = 0x9E3779B97F4A7C15ull;  // the empty text
+
+// The hash of a text with one more label (the result never depends on it: nb_same_text).
+__device__ __forceinline__ unsigned long long nb_mix(unsigned long long h, uint32_t label,
+                                                     unsigned long long mask) {
+  h = (h ^ label) * 0xD6E8FEB86659FD93ull;
+  h ^= h >> 32;
+  h *= 0xD6E8FEB86659FD93ull;
+  return (h ^ (h >> 29)) & mask;
+}
+
+// One step of a walk back through a prefix: from list entry (s, r) to the entry of its rest,
+// over every arc of an epsilon olabel.  Returns the next label of the text, read backwards, or
+// 0 at the empty prefix ((s, r) is then the start's entry).  steps counts the arcs taken: a
+// prefix has fewer than the item has states.
 template <bool kLds>
-__device__ __forceinline__ void nb_pull(const NbItem& it, const NbTables& T, uint32_t n,
-                                        uint32_t t) {
+__device__ __forceinline__ uint32_t nb_text_back(const NbItem& it, const NbTables& T, uint32_t n,
+                                                 uint32_t& s, uint32_t& r, uint32_t& steps,
+                                                 bool& bad) {
+  for (;;) {
+    const unsigned long long ar = nb_ld<kLds>(&T.ear[(size_t)s * n + r]);
+    const uint32_t a = (uint32_t)(ar >> 32);
+    if (a == kNbNoArc) return 0;
+    r = (uint32_t)ar;
+    if (a >= it.A || r >= n || ++steps >= it.S) break;
+    s = nb_ld<kLds>(&T.asrc[a]);
+    if (s >= it.S) break;
+    const uint32_t l = it.aol[a];
+    if (l) return l;
+  }
+  bad = true;
+  return 0;
+}
+
+// Whether two prefixes print the same text.  A prefix is a list entry (s, r) with s < S and
+// r < n, plus one pending label in front of it (0: none), which is how a candidate that is in no
+// list yet is given: its last arc's olabel and its source entry.  The texts are compared from
+// their ends; they are equal if both walks reach the empty prefix together, or meet in one
+// entry with nothing pending.  `bad`: a walk broke its bound or read a bad index.
+template <bool kLds>
+__device__ __forceinline__ bool nb_same_text(const NbItem& it, const NbTables& T, uint32_t n,
+                                             uint32_t la, uint32_t sa, uint32_t ra, uint32_t lb,
+                                             uint32_t sb, uint32_t rb, bool& bad) {
+  uint32_t na = 0, nb = 0;
+  for (;;) {
+    if (!la && !lb && sa == sb && ra == rb) return true;
+    if (!la) la = nb_text_back<kLds>(it, T, n, sa, ra, na, bad);
+    if (!lb) lb = nb_text_back<kLds>(it, T, n, sb, rb, nb, bad);
+    if (bad || la != lb) return false;
+    if (!la) return true;  // both at the empty prefix
+    la = lb = 0;
+  }
+}
+
+// E(t) of one state, by one lane: see the file comment.  kUnique: Eu(t), the at most n least
+// prefixes with pairwise different texts; a candidate whose text the list holds takes that
+// entry's place if it comes before it and is passed over otherwise.  False: a walk broke.
+template <bool kLds, bool kUnique>
+__device__ __forceinline__ bool nb_pull(const NbItem& it, const NbTables& T, uint32_t n,
+                                        uint32_t t, unsigned long long hmask) {
   const size_t eb = (size_t)t * n;
   uint32_t c = 0;
+  bool bad = false;
   if (t == it.start) {
     T.eg[eb] = (unsigned long long)__double_as_longlong(0.0);
     T.ear[eb] = (unsigned long long)kNbNoArc << 32;
+    if constexpr (kUnique) T.eh[eb] = kNbHashSeed & hmask;
     c = 1;
   } else {
     const uint32_t q0 = t ? nb_ld<kLds>(&T.roff[t - 1]) : 0u;
@@ -191,10 +263,13 @@ __device__ __forceinline__ void nb_pull(const NbItem& it, const NbTables& T, uin
       uint32_t cs = nb_ld<kLds>(&T.cnt[s]);
       cs = cs < n ? cs : n;
       const size_t sbs = (size_t)s * n;
+      uint32_t ol = 0;
+      if constexpr (kUnique) ol = it.aol[a];
       for (uint32_t r = 0; r < cs; ++r) {
         const double g = __longlong_as_double((long long)nb_ld<kLds>(&T.eg[sbs + r])) + w;
         if (nb_is_zero(g)) break;  // (the rest of the source list costs no less)
         const unsigned long long ar = ((unsigned long long)a << 32) | r;
+        [[maybe_unused]] const bool full = c == n;
         uint32_t pos;
         if (c == n) {  // full: the candidate replaces the last entry or the arc is done
           pos = n - 1;
@@ -203,27 +278,59 @@ __device__ __forceinline__ void nb_pull(const NbItem& it, const NbTables& T, uin
         } else {
           pos = c++;
         }
+        [[maybe_unused]] unsigned long long h = 0;
+        if constexpr (kUnique) {
+          h = nb_ld<kLds>(&T.eh[sbs + r]);
+          if (ol) h = nb_mix(h, ol, hmask);
+          // the entry of the same text, if the list holds one (entries 0 .. have - 1)
+          const uint32_t have = full ? n : pos;
+          uint32_t twin = have;
+          for (uint32_t j = 0; j < have && !bad; ++j) {
+            if (T.eh[eb + j] != h) continue;
+            if (nb_same_text<kLds>(it, T, n, ol, s, r, 0u, t, j, bad)) {
+              twin = j;
+              break;
+            }
+          }
+          if (bad) {
+            if (!full) --c;
+            break;
+          }
+          if (twin < have) {
+            if (!full) --c;  // (the list does not grow)
+            if (!nb_less(g, ar, __longlong_as_double((long long)T.eg[eb + twin]),
+                         T.ear[eb + twin]))
+              continue;  // the twin is before the candidate: on to the next rank
+            pos = twin;  // the candidate takes its place
+          }
+        }
         // (the lane's own list: its own stores, read back in program order)
         while (pos > 0) {
           const unsigned long long pg = T.eg[eb + pos - 1], par = T.ear[eb + pos - 1];
           if (!nb_less(g, ar, __longlong_as_double((long long)pg), par)) break;
           T.eg[eb + pos] = pg;
           T.ear[eb + pos] = par;
+          if constexpr (kUnique) T.eh[eb + pos] = T.eh[eb + pos - 1];
           --pos;
         }
         T.eg[eb + pos] = (unsigned long long)__double_as_longlong(g);
         T.ear[eb + pos] = ar;
+        if constexpr (kUnique) T.eh[eb + pos] = h;
       }
+      if (bad) break;
     }
   }
   T.cnt[t] = c;
+  return !bad;
 }
 
 // One item, by the whole workgroup (every thread calls; SH and T are the item's).
-template <int WG, bool kLds>
+// SH is an NbShared, for kUnique an NbSharedUnique; hmask: FSTAMD_NBEST_HASH_MASK (kUnique).
+template <int WG, bool kLds, bool kUnique, class Shared>
 __device__ __forceinline__ void nbest_item(const NbItem& it, const NbTables& T, uint32_t n,
-                                           const BatchOutDev& out, uint32_t si, NbShared& SH,
-                                           unsigned long long deadline) {
+                                           const BatchOutDev& out, uint32_t si, Shared& SH,
+                                           unsigned long long deadline,
+                                           unsigned long long hmask) {
   const uint32_t tid = threadIdx.x, S = it.S, A = it.A;
   // ---- 1: depth -----------------------------------------------------------------------
   for (uint32_t s = tid; s < S; s += WG) {
@@ -314,14 +421,18 @@ __device__ __forceinline__ void nbest_item(const NbItem& it, const NbTables& T, 
     }
     for (uint32_t i = lo + tid; i < hi; i += WG) {
       const uint32_t t = nb_ld<kLds>(&T.order[i]);
-      if (t < S) nb_pull<kLds>(it, T, n, t);
+      if (t < S && !nb_pull<kLds, kUnique>(it, T, n, t, hmask)) SH.stop = 1;
     }
     nb_sync<kLds>();
+  }
+  if constexpr (kUnique) {  // (a text walk that broke its bound; read after the level's barrier)
+    if (SH.stop) return nb_status<WG>(out, si, n, kPathInternal, it);
   }
   // ---- 4: the n best complete paths, by (total, final state, rank) -----------------------
   uint32_t m = 0;
   unsigned long long last_k = 0, last_t = 0;
-  for (uint32_t k = 0; k < n; ++k) {
+  // One round: the least (total, t, r) above the round before, ~0 if there is none (uniform).
+  const auto round_min = [&](bool k, unsigned long long& mk) {
     unsigned long long bk = ~0ull, bt = ~0ull;
     for (uint32_t t = tid; t < S; t += WG) {
       if (!nb_ld<kLds>(&T.depth[t])) continue;
@@ -343,13 +454,52 @@ __device__ __forceinline__ void nbest_item(const NbItem& it, const NbTables& T, 
         break;
       }
     }
-    const unsigned long long mk = nb_block_min<WG>(bk, SH);
-    const unsigned long long mt = nb_block_min<WG>(bk == mk ? bt : ~0ull, SH);
-    if (mt == ~0ull) break;  // (uniform) fewer than n complete paths
-    if (tid == 0) SH.sel[k] = mt;
-    last_k = mk;
-    last_t = mt;
-    ++m;
+    mk = nb_block_min<WG>(bk, SH);
+    return nb_block_min<WG>(bk == mk ? bt : ~0ull, SH);
+  };
+  if constexpr (!kUnique) {
+    for (uint32_t k = 0; k < n; ++k) {
+      unsigned long long mk;
+      const unsigned long long mt = round_min(k != 0, mk);
+      if (mt == ~0ull) break;  // (uniform) fewer than n complete paths
+      if (tid == 0) SH.sel[k] = mt;
+      last_k = mk;
+      last_t = mt;
+      ++m;
+    }
+  } else {
+    // The same rounds; a winner whose text was chosen before advances (last_k, last_t) without
+    // taking a slot.  Every wave compares the winner with the chosen paths for itself, lane j
+    // with path j, so the verdict is uniform without a word of LDS.  A round passes one (final
+    // state, rank) entry: there are at most S * n.
+    const unsigned long long rounds = (unsigned long long)S * n;
+    for (unsigned long long round = 0; m < n && round < rounds; ++round) {
+      if ((round & 15u) == 15u) {
+        if (tid == 0 && __builtin_amdgcn_s_memrealtime() > deadline) SH.stop = 1;
+        nb_sync<kLds>();
+        if (SH.stop) return nb_status<WG>(out, si, n, kPathInternal, it);
+      }
+      unsigned long long mk;
+      const unsigned long long mt = round_min(round != 0, mk);
+      if (mt == ~0ull) break;  // (uniform) fewer than n distinct texts
+      last_k = mk;
+      last_t = mt;
+      const uint32_t wt = (uint32_t)(mt >> 32), wr = (uint32_t)mt;  // (wt < S, wr < n: as scanned)
+      const unsigned long long wh = nb_ld<kLds>(&T.eh[(size_t)wt * n + wr]);
+      const uint32_t j = tid & 63u;
+      bool bad = false, twin = false;
+      if (j < m && SH.selh[j] == wh) {
+        const unsigned long long e = SH.sel[j];
+        twin = nb_same_text<kLds>(it, T, n, 0u, wt, wr, 0u, (uint32_t)(e >> 32), (uint32_t)e, bad);
+      }
+      if (__ballot(bad)) return nb_status<WG>(out, si, n, kPathInternal, it);
+      if (__ballot(twin)) continue;
+      if (tid == 0) {
+        SH.sel[m] = mt;
+        SH.selh[m] = wh;
+      }
+      ++m;  // (the other waves read sel and selh behind the next round's barriers)
+    }
   }
   nb_sync<kLds>();
   if (tid >= 64) return;
@@ -412,18 +562,23 @@ __device__ __forceinline__ void nbest_item(const NbItem& it, const NbTables& T, 
   }
 }
 
-// The LDS an item's tables take: 16 B per list entry, five words per state, two per arc.
+// The LDS an item's tables take: 16 B per list entry (24 B with the text hashes of kUnique),
+// five words per state, two per arc.
 __host__ __device__ __forceinline__ unsigned long long nb_lds_need(uint32_t S, uint32_t A,
                                                                    uint32_t n) {
   return 16ull * n * S + 4ull * (5ull * S + 2ull * A);
 }
+__host__ __device__ __forceinline__ unsigned long long nb_lds_need_unique(uint32_t S, uint32_t A,
+                                                                          uint32_t n) {
+  return 24ull * n * S + 4ull * (5ull * S + 2ull * A);
+}
 
 // ---- LDS tier: one wave per item, the tables in dynamic LDS of p.lds_budget bytes -----------
 // An item whose tables do not fit is handed to the HBM tier through p.list.
-__global__ void __launch_bounds__(64)
-lattice_nbest_lds_kernel(LatNbestDev p, uint32_t count, BatchOutDev out) {
-  extern __shared__ __align__(16) unsigned char nb_lds[];
-  __shared__ NbShared SH;
+template <bool kUnique, class Shared>
+__device__ __forceinline__ void nb_lds_tier(const LatNbestDev& p, uint32_t count,
+                                            const BatchOutDev& out, unsigned char* nb_lds,
+                                            Shared& SH) {
   const uint32_t n = p.n_best;
   uint32_t done = 0;  // (one atomic per wave, not per item)
   for (uint32_t si = blockIdx.x; si < count; si += gridDim.x) {
@@ -432,14 +587,17 @@ lattice_nbest_lds_kernel(LatNbestDev p, uint32_t count, BatchOutDev out) {
       ++done;
       continue;
     }
-    if (nb_lds_need(it.S, it.A, n) > p.lds_budget) {  // (uniform)
+    const unsigned long long need =
+        kUnique ? nb_lds_need_unique(it.S, it.A, n) : nb_lds_need(it.S, it.A, n);
+    if (need > p.lds_budget) {  // (uniform)
       if (threadIdx.x == 0) p.list[atomicAdd(&p.ctr[kNbCtrList], 1u)] = si;
       continue;
     }
     NbTables T;
     T.eg = reinterpret_cast<unsigned long long*>(nb_lds);
     T.ear = T.eg + (size_t)it.S * n;
-    T.depth = reinterpret_cast<uint32_t*>(T.ear + (size_t)it.S * n);
+    T.eh = kUnique ? T.ear + (size_t)it.S * n : nullptr;
+    T.depth = reinterpret_cast<uint32_t*>(T.ear + (size_t)it.S * n * (kUnique ? 2 : 1));
     T.roff = T.depth + it.S;
     T.cnt = T.roff + it.S;
     T.lvl = T.cnt + it.S;
@@ -447,18 +605,33 @@ lattice_nbest_lds_kernel(LatNbestDev p, uint32_t count, BatchOutDev out) {
     T.rarc = T.order + it.S;
     T.asrc = T.rarc + it.A;
     ++done;
-    nbest_item<64, true>(it, T, n, out, si, SH, __builtin_amdgcn_s_memrealtime() + p.wd_ticks);
+    nbest_item<64, true, kUnique>(it, T, n, out, si, SH,
+                                  __builtin_amdgcn_s_memrealtime() + p.wd_ticks, p.hash_mask);
     __syncthreads();  // (SH and the tables are the next item's)
   }
   if (threadIdx.x == 0 && done) atomicAdd(&p.ctr[kNbCtrLds], done);
 }
 
+__global__ void __launch_bounds__(64)
+lattice_nbest_lds_kernel(LatNbestDev p, uint32_t count, BatchOutDev out) {
+  extern __shared__ __align__(16) unsigned char nb_lds[];
+  __shared__ NbShared SH;
+  nb_lds_tier<false>(p, count, out, nb_lds, SH);
+}
+
+__global__ void __launch_bounds__(64)
+lattice_nbest_unique_lds_kernel(LatNbestDev p, uint32_t count, BatchOutDev out) {
+  extern __shared__ __align__(16) unsigned char nb_lds[];
+  __shared__ NbSharedUnique SH;
+  nb_lds_tier<true>(p, count, out, nb_lds, SH);
+}
+
 // ---- HBM tier: one workgroup per listed item, the tables in the workspace -----------------
 // The item's slices: list entries at state_base * n, state words at state_base, arc words at
 // arc_base.
-__global__ void __launch_bounds__(kNbWG)
-lattice_nbest_hbm_kernel(LatNbestDev p, BatchOutDev out) {
-  __shared__ NbShared SH;
+template <bool kUnique, class Shared>
+__device__ __forceinline__ void nb_hbm_tier(const LatNbestDev& p, const BatchOutDev& out,
+                                            Shared& SH) {
   const uint32_t n = p.n_best;
   const uint32_t count = p.ctr[kNbCtrList];
   for (uint32_t li = blockIdx.x; li < count; li += gridDim.x) {
@@ -468,6 +641,7 @@ lattice_nbest_hbm_kernel(LatNbestDev p, BatchOutDev out) {
     NbTables T;
     T.eg = p.eg + it.sb * n;
     T.ear = p.ear + it.sb * n;
+    T.eh = kUnique ? p.eh + it.sb * n : nullptr;
     T.depth = p.depth + it.sb;
     T.roff = p.roff + it.sb;
     T.cnt = p.cnt + it.sb;
@@ -475,11 +649,24 @@ lattice_nbest_hbm_kernel(LatNbestDev p, BatchOutDev out) {
     T.order = p.order + it.sb;
     T.rarc = p.rarc + it.ab;
     T.asrc = p.asrc + it.ab;
-    nbest_item<kNbWG, false>(it, T, n, out, si, SH,
-                             __builtin_amdgcn_s_memrealtime() + p.wd_ticks);
+    nbest_item<kNbWG, false, kUnique>(it, T, n, out, si, SH,
+                                      __builtin_amdgcn_s_memrealtime() + p.wd_ticks,
+                                      p.hash_mask);
     if (threadIdx.x == 0) atomicAdd(&p.ctr[kNbCtrHbm], 1u);
     __syncthreads();  // (SH is the next item's)
   }
+}
+
+__global__ void __launch_bounds__(kNbWG)
+lattice_nbest_hbm_kernel(LatNbestDev p, BatchOutDev out) {
+  __shared__ NbShared SH;
+  nb_hbm_tier<false>(p, out, SH);
+}
+
+__global__ void __launch_bounds__(kNbWG)
+lattice_nbest_unique_hbm_kernel(LatNbestDev p, BatchOutDev out) {
+  __shared__ NbSharedUnique SH;
+  nb_hbm_tier<true>(p, out, SH);
 }
 
 }  // namespace fstamd

@@ -184,6 +184,12 @@ SIGNATURES = {
     "fst_device_nbest_lhs": (
         C.c_int, [C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceBatch), _P]),
+    "fst_nbest_unique_lhs_batch": (
+        C.c_int, [C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstBatchResult)]),
+    "fst_device_nbest_unique_lhs": (
+        C.c_int, [C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstDeviceBatch), _P]),
     "fst_device_compose_frozen": (
         C.c_int, [_u64, _P, _P, _u32, _u32, _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceLattices), C.POINTER(_u64), _P]),
@@ -658,12 +664,24 @@ def nbest_lhs_batch(lhs: LhsBatch, n: int, device: int = -1, devices=None,
     """The n best distinct paths of every item of an lhs batch of acyclic items
     (fst_nbest_lhs_batch; the order is defined in fst_batch.h): a BatchResult of len(lhs) * n
     strings, item i's k-th best at i * n + k, EMPTY past the item's last path."""
+    return _nbest("fst_nbest_lhs_batch", lhs, n, device, devices, shards)
+
+
+def nbest_unique_lhs_batch(lhs: LhsBatch, n: int, device: int = -1, devices=None,
+                           shards: int = 0) -> BatchResult:
+    """The n best paths with pairwise different output texts (the non-epsilon olabels) of every
+    item of an lhs batch of acyclic items (fst_nbest_unique_lhs_batch): nbest_lhs_batch's order
+    with every path dropped that prints the text of an earlier one; the same layout."""
+    return _nbest("fst_nbest_unique_lhs_batch", lhs, n, device, devices, shards)
+
+
+def _nbest(entry, lhs, n, device, devices, shards):
     opts = batch_options(device, FST_SEM_LAZY, devices, shards)
     res = FstBatchResult()
     cs = lhs.c_struct()
-    rc = lib().fst_nbest_lhs_batch(C.byref(cs), n, C.byref(opts), C.byref(res))
+    rc = getattr(lib(), entry)(C.byref(cs), n, C.byref(opts), C.byref(res))
     if rc != FST_OK:
-        raise RuntimeError(f"fst_nbest_lhs_batch failed: {rc}")
+        raise RuntimeError(f"{entry} failed: {rc}")
     return _take_result(res, len(lhs) * n)
 
 

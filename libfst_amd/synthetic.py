@@ -181,3 +181,16 @@ def nbest_union(rng, texts):
         if finals[s] == INF:
             finals[s] = float(rng.random())
     return 0, finals, arcs
+
+
+def respelled_union(rng, text, k):
+    """An nbest_union of up to k hypotheses of `text` that differ in how its digits are written:
+    the first is `text`, every other spells each digit as its WORDS entry with probability 1/2
+    (equal hypotheses fall together).  After tagger -> verbalizer a kept digit can come out as
+    its word too, so paths of different hypotheses print equal texts: the repeats that
+    fst_nbest_unique_lhs_batch removes."""
+    hyps = [text]
+    for _ in range(k - 1):
+        hyps.append("".join(WORDS[int(c)] if c in DIGITS and rng.random() < 0.5 else c
+                            for c in text))
+    return nbest_union(rng, hyps)
