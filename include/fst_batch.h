@@ -491,6 +491,76 @@ FstError fst_device_compose_frozen(FstHandle b, const uint32_t* d_labels, const 
                                    const FstBatchOptions* opts, const FstDeviceLattices* out,
                                    uint64_t needed[2], void* stream);
 
+/* Beam pruning of every item of an lhs batch: what OpenFst and Kaldi callers know as fstprune /
+ * Prune(beam), run before a rescoring pass, a second grammar or an n-best.  Connect drops dead
+ * ends; this drops what is alive but hopeless: arcs and final weights that lie only on paths
+ * worse than the best one by more than `beam`.  The reference has no prune, so the definition is
+ * this comment.
+ *
+ * Items and statuses.  An item has states 0 .. S-1, arcs in CSR and a start; arc a runs
+ * src(a) -> dst(a) with weight w(a).  A state is final when its final weight is not +-inf
+ * (connect's rule).  Tested in this order:
+ *   1. no start, or zero states: FST_PATH_OK with the empty FST (zero states, start =
+ *      FST_NO_STATE), as connect gives;
+ *   2. a NaN arc or final weight anywhere in the item, or an arc weight w < 0.0 (-inf included;
+ *      -0.0 is not < 0.0: it is accepted and acts as zero): FST_PATH_UNSUPPORTED with zero
+ *      states and start = FST_NO_STATE.  Final weights may be negative.  An arc of weight +inf
+ *      is accepted and is never part of a path;
+ *   3. (device entry) an item the prepare kernel refuses: FST_PATH_UNSUPPORTED, the other items
+ *      unaffected, exactly as for fst_device_shortest_path_lhs;
+ *   4. otherwise FST_PATH_OK with the result below.
+ * Distances.  Both are minima over f64 values and nothing else.
+ *   F(s) = the minimum over paths from the start to s of the LEFT fold ((0.0 + w_1) + w_2) + ...;
+ *     F(start) = 0.0, F(s) = +inf when s is not reachable (fst_shortest_path_lhs_batch's
+ *     distance on items of non-negative weights).
+ *   B(s) = the minimum over paths from s to a final state t of the RIGHT fold
+ *     w_1 + (w_2 + (... + (w_k + final(t)))); the empty path gives final(s); B(s) = +inf when no
+ *     final state is reachable.  As a recurrence:
+ *     B(s) = min(final(s) if final, min over arcs a out of s of fl(w(a) + B(dst(a)))).
+ *   With every arc weight >= 0, fl(x + w) >= x, so both are the fixpoints that any order of
+ *   relaxations reaches from +inf; B is the same problem on the reversed arcs with several
+ *   sources, because fl(a + b) = fl(b + a).  Cycles are therefore allowed.
+ * The cut.
+ *   best = min over final t of fl(F(t) + final(t)), a THIRD sum.  best = +inf: the result is the
+ *     empty FST, status OK.
+ *   limit = fl(best + beam).
+ *   Arc a is kept iff T(a) = fl(fl(F(src(a)) + w(a)) + B(dst(a))) is not +inf and T(a) <= limit.
+ *   State s keeps its final weight iff it is final and fl(F(s) + final(s)) is not +inf and is
+ *     <= limit; otherwise its final weight becomes +inf.
+ *   All comparisons are on f64 values: -0.0 equals +0.0.
+ * The result is connect, by fst_connect_lhs_batch's definition word for word, of the item with
+ * only the kept arcs and the kept finals: the kept states renumbered by increasing old id, arcs
+ * in their old order, labels and weight bits copied; a start that is not kept gives the empty
+ * FST.  (The connect step is needed: in exact arithmetic a kept arc's src is reachable over kept
+ * arcs; under rounding that is not guaranteed.)
+ * What this means.  F is a left fold, B a right fold and best a third sum.  When every sum is
+ * exact -- integer or dyadic weights of bounded size -- the result is exactly the states and arcs
+ * on some complete path of total <= best + beam, and the 1-best path survives at beam = 0.  With
+ * arbitrary f64 weights T on the best path can exceed best by rounding: a caller who needs the
+ * best path kept must give the beam that slack.  The final state that attains best always keeps
+ * its final weight (beam >= 0 and fl is monotone).  beam = +inf keeps everything of finite
+ * total: on an item without +inf arcs and without sums that overflow this is connect.
+ *
+ * Validation.  A beam that is NaN or < 0.0 returns FST_INVALID_ARG (tested before lhs's arrays
+ * are read; -0.0 is valid).  Otherwise the same validator as every lhs entry: *out zeroed on
+ * error, a null lhs / out and unknown opts->flags rejected.  num_fsts == 0 gives the empty OK
+ * result.  opts->semantics is ignored.  FST_BATCH_DEVICES shards by arcs + 1 per item; a sharded
+ * result is byte-identical to a one-shard run.  Free with fst_lattice_batch_free.
+ * fst_last_launch_stats reports engine 15. */
+FstError fst_prune_lhs_batch(const FstLhsBatch* lhs, double beam, const FstBatchOptions* opts,
+                             FstLatticeBatch* out);
+
+/* Device-resident: d_lhs as for fst_device_shortest_path_lhs (a host struct of device pointers,
+ * trusted extents, per-item validation by the prepare kernel), out and needed as for
+ * fst_device_compose_frozen: needed receives the pruned totals; when either exceeds its capacity
+ * only `status` and `needed` are defined and nothing past a capacity is written.  num_fsts == 0:
+ * needed = {0, 0}, state_offsets[0] = 0 and arc_offsets[0] = 0 are written.  The call
+ * SYNCHRONISES `stream`.  The result chains into every device lhs entry, so chains -> lattices ->
+ * prune -> unique n-best -> text never leaves the device.  Engine 15; `launches` counts the
+ * preparation kernels too. */
+FstError fst_device_prune_lhs(const FstLhsBatch* d_lhs, double beam, const FstBatchOptions* opts,
+                              const FstDeviceLattices* out, uint64_t needed[2], void* stream);
+
 /* Text in, text out: the loop the reference application runs per utterance and stage,
  *   fst_compile_string(bytes) -> fst_compose_frozen_shortest_path -> fst_print_output_string
  * (README.md:177-214, src/string.zig:17-97), for a whole batch with bytes on both sides of
@@ -675,7 +745,10 @@ typedef struct {
                                         lattice with them in HBM behind it),
                                    14 = fst_nbest_unique_lhs_batch and
                                         fst_device_nbest_unique_lhs (engine 13's two tiers with
-                                        a text hash per list entry) */
+                                        a text hash per list entry),
+                                   15 = fst_prune_lhs_batch and fst_device_prune_lhs (one wave
+                                        per lattice for both distances and the cut, a workgroup
+                                        per lattice behind it, then the trim kernels) */
     uint32_t grid;              /* workgroups of the dominant kernel */
 } FstLaunchStats;
 FstError fst_last_launch_stats(FstLaunchStats* out);

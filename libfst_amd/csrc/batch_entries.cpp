@@ -508,6 +508,18 @@ FstError fst_connect_lhs_batch(const FstLhsBatch* lhs, const FstBatchOptions* op
                      [&](Shard& S, const BatchCall&) { return run_connect_shard(S, *lhs); });
 }
 
+// Beam pruning of every item of an lhs batch: staged as connect stages them, then the cut and the
+// trim on a shadow of the staged items (run_prune_shard).
+FstError fst_prune_lhs_batch(const FstLhsBatch* lhs, double beam, const FstBatchOptions* opts,
+                             FstLatticeBatch* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  // (the beam before the validator, which reads lhs's arrays; !(beam >= 0): NaN too)
+  if (!(beam >= 0.0) || !lhs_batch_valid(lhs) || !flags_ok(opts)) return FST_INVALID_ARG;
+  return lhs_sharded(lhs, opts, true, out, "fst_prune_lhs_batch", fst_lattice_batch_free,
+                     [&](Shard& S, const BatchCall&) { return run_prune_shard(S, *lhs, beam); });
+}
+
 // fst_shortest_path of every item of an lhs batch: no rhs, no compose; the items are staged as
 // the lhs entries stage them and reduced to their 1-best paths in place (run_sp_shard).
 FstError fst_shortest_path_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
@@ -661,6 +673,53 @@ FstError fst_device_shortest_path_lhs(const FstLhsBatch* d_lhs, uint32_t n,
   t_last_stats = st;
   call.drain.done = true;  // (run_sp_batch synchronised the stream)
   return FST_OK;
+}
+
+// Beam pruning of a device-resident lhs batch: prepared like the shortest path's, the cut and the
+// trim on a shadow of the caller's arrays (prune_lattices), then fst_device_compose_frozen's
+// compaction straight into the caller's result when it holds the pruned batch.
+FstError fst_device_prune_lhs(const FstLhsBatch* d_lhs, double beam, const FstBatchOptions* opts,
+                              const FstDeviceLattices* o, uint64_t needed[2], void* stream) {
+  if (!(beam >= 0.0) || !device_lhs_args_ok(d_lhs) || !o || !needed || !flags_ok(opts))
+    return FST_INVALID_ARG;
+  const uint32_t num = d_lhs->num_fsts;
+  if (!o->state_offsets || !o->arc_offsets || (num && (!o->status || !o->start)))
+    return FST_INVALID_ARG;
+  if ((o->state_capacity && !o->final_weights) ||
+      (o->arc_capacity && (!o->ilabels || !o->olabels || !o->weights || !o->nextstates)))
+    return FST_INVALID_ARG;
+  // (declared before the frame's drain, so destroyed after it: the gather reads them)
+  std::unique_ptr<LatShard> lat;
+  std::unique_ptr<DevOut> keep;
+  DeviceCall call;
+  if (FstError e = call.open(opts, nullptr, stream); e != FST_OK) return e;
+  const hipStream_t s = call.s;
+  needed[0] = needed[1] = 0;
+  if (num == 0) {
+    LaunchStats st;
+    st.engine = 15;
+    t_last_stats = st;
+    return hipMemsetAsync(o->state_offsets, 0, 8, s) == hipSuccess &&
+                   hipMemsetAsync(o->arc_offsets, 0, 8, s) == hipSuccess
+               ? FST_OK
+               : FST_OOM;
+  }
+  LhsBatchDev batch;
+  LhsPrepared p;
+  if (FstError e = device_lhs_prepare(call, d_lhs, &batch, &p); e != FST_OK) return e;
+  if (FstError e = prune_lattices(call.E, batch, beam, p.launches, s, &lat, &keep); e != FST_OK)
+    return e;
+  const LatticeCsrDev csr{o->status,      o->state_offsets, o->start,   o->final_weights,
+                          o->arc_offsets, o->ilabels,       o->olabels, o->weights,
+                          o->nextstates,  o->state_capacity, o->arc_capacity};
+  const LatticeOutDev& arena = lat->arena.v;
+  if (call.E->compact_lattices_count(keep->v.status, arena, num, csr, needed, s) != hipSuccess)
+    return FST_OOM;
+  if (needed[0] > arena.state_cap || needed[1] > arena.arc_cap) return FST_OOM;
+  // too small: the statuses and `needed` stand, nothing else is written
+  if (needed[0] > csr.state_cap || needed[1] > csr.arc_cap) return FST_OK;
+  if (call.E->compact_lattices(arena, num, csr, s, &lat->trim.v) != hipSuccess) return FST_OOM;
+  return FST_OK;  // (the drain waits for the gather, then `keep` and `lat` go)
 }
 
 // The n best paths of a device-resident lhs batch: prepared like the shortest path's, then

@@ -1,8 +1,8 @@
 // batch_lhs.cpp -- host batches of general lhs (lattices, confusion networks) and the lattice
 // batch: the staging of a shard's items into one block (stage_lhs_items), the shard steps on it
-// (1-best, pipelines on a general first stage, shortest path, n-best, connect), the lattice arena
-// with its reruns, the trim driver, the two lattice shard steps, and the lattice sink of
-// run_sharded.
+// (1-best, pipelines on a general first stage, shortest path, n-best, connect, prune), the lattice
+// arena with its reruns, the trim and prune drivers, the two lattice shard steps, and the lattice
+// sink of run_sharded.
 // run_arena, run_sharded itself and the chain stages: batch_sharded.cpp.
 #include <cmath>
 
@@ -207,7 +207,8 @@ bool alloc_lattice_result(FstLatticeBatch* out, uint32_t num, uint64_t states, u
 // ---- Lattice trim (connect) ---------------------------------------------------------------
 
 FstError trim_lattices(DeviceEngine::Lease& E, const int32_t* status, LatShard& L, uint32_t num,
-                       hipStream_t stream) {
+                       hipStream_t stream, unsigned long long* totals) {
+  if (totals) std::memset(totals, 0, 4 * sizeof(*totals));
   if (num == 0) return FST_OK;
   const LatticeOutDev& a = L.arena.v;
   LatShard::Trim& W = L.trim;
@@ -288,6 +289,7 @@ FstError trim_lattices(DeviceEngine::Lease& E, const int32_t* status, LatShard& 
   if (hipEventElapsedTime(&ms, ev.e[0], ev.e[1]) != hipSuccess) ms = 0.f;
   t_last_stats.kernel_ms += ms;
   t_last_stats.launches += launches;
+  if (totals) std::memcpy(totals, back.data(), 4 * sizeof(*totals));
   if (std::getenv("FSTAMD_ROUTE_LOG")) {
     unsigned long long tot[4];
     std::memcpy(tot, back.data(), sizeof(tot));
@@ -341,6 +343,82 @@ FstError run_connect_shard(Shard& S, const FstLhsBatch& L) {
   Lt->arena.input = std::move(st);
   S.lat = std::move(Lt);
   S.keep = std::move(out);
+  return FST_OK;
+}
+
+// ---- Lattice prune (beam) -----------------------------------------------------------------
+
+FstError prune_lattices(DeviceEngine::Lease& E, const LhsBatchDev& b, double beam,
+                        uint32_t prep_launches, hipStream_t stream,
+                        std::unique_ptr<LatShard>* lat, std::unique_ptr<DevOut>* keep) {
+  const uint32_t num = b.in.num_strings;
+  auto Lt = std::make_unique<LatShard>();
+  auto out = std::make_unique<DevOut>(num, 1);  // the statuses
+  // every return drains the stream before the shadow arrays and the trim's workspace go
+  StreamDrain drain{{stream}};
+  Lt->arena.item = std::make_unique<DevBuf>(std::max<size_t>(num, 1) * sizeof(LatItem));
+  Lt->arena.fin = std::make_unique<DevBuf>((b.total_states + 4) * 8);
+  Lt->arena.next = std::make_unique<DevBuf>((b.total_arcs + 4) * 4);
+  Lt->trim.start = std::make_unique<DevBuf>(std::max<size_t>(num, 1) * 4ull);
+  if (!out->ok() || !Lt->arena.item->p || !Lt->arena.fin->p || !Lt->arena.next->p ||
+      !Lt->trim.start->p)
+    return FST_OOM;
+  // the arena is the batch itself, read in place (item i's arc offsets sit i words on), with
+  // the mark pass's finals and targets in place of its own
+  const GraphInput& g = b.lhs;
+  LatticeOutDev& a = Lt->arena.v;
+  a.item = (LatItem*)Lt->arena.item->p;
+  a.fin = (double*)Lt->arena.fin->p;
+  a.aoff = const_cast<uint32_t*>(g.state_off);
+  a.il = const_cast<uint32_t*>(g.arc_il);
+  a.ol = const_cast<uint32_t*>(g.arc_ol);
+  a.w = const_cast<double*>(g.arc_w);
+  a.next = (uint32_t*)Lt->arena.next->p;
+  a.state_cap = b.total_states;
+  a.arc_cap = b.total_arcs;
+  Lt->connect = true;
+  Lt->trim.v.aoff_skew = 1;
+  LatPruneDev v{};
+  v.item = a.item;
+  v.status = out->v.status;
+  v.start = (uint32_t*)Lt->trim.start->p;
+  v.sfin = a.fin;
+  v.snext = a.next;
+  LaunchStats ls;
+  LhsRoute route;
+  const hipError_t err = E->run_prune_batch(b, beam, v, stream, &ls, &route);
+  if (err != hipSuccess) {
+    std::fprintf(stderr, "[libfst_amd] lattice prune failed: %s\n", hipGetErrorString(err));
+    return FST_OOM;
+  }
+  ls.launches += prep_launches;
+  t_last_stats = ls;
+  unsigned long long tot[4];
+  if (FstError e = trim_lattices(E, out->v.status, *Lt, num, stream, tot); e != FST_OK) return e;
+  drain.done = true;  // (trim_lattices synchronised it)
+  if (std::getenv("FSTAMD_ROUTE_LOG"))
+    std::fprintf(stderr,
+                 "[libfst_amd route] lattice prune: items %u | wave %u frontier %u | states %llu -> "
+                 "%llu arcs %llu -> %llu | %.3f ms\n",
+                 num, route.t[0], route.t[1], tot[0], tot[1], tot[2], tot[3],
+                 t_last_stats.kernel_ms);
+  *lat = std::move(Lt);
+  *keep = std::move(out);
+  return FST_OK;
+}
+
+FstError run_prune_shard(Shard& S, const FstLhsBatch& L, double beam) {
+  const int dev = S.E->dev();
+  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  const hipStream_t stream = S.E.stream();
+  auto st = std::make_shared<LhsStaged>();
+  // every return drains the stream before the staged blocks go
+  StreamDrain drain{{stream}};
+  if (FstError e = stage_lhs_items(S, nullptr, L, stream, st.get()); e != FST_OK) return e;
+  if (FstError e = prune_lattices(S.E, st->b, beam, 0, stream, &S.lat, &S.keep); e != FST_OK)
+    return e;
+  drain.done = true;  // (prune_lattices synchronised it)
+  S.lat->arena.input = std::move(st);
   return FST_OK;
 }
 

@@ -472,6 +472,10 @@ enum Scratch : size_t {
   kNbWork,
   kNbList,
   kNbCtr,
+  kPrKey,
+  kPrWork,
+  kPrList,
+  kPrCtr,
   kNumScratch
 };
 
@@ -3223,6 +3227,81 @@ hipError_t DeviceEngine::run_nbest_batch(const LhsBatchDev& b, uint32_t n, bool 
     *route = LhsRoute();
     route->t[0] = ctr[kNbCtrLds];
     route->t[1] = ctr[kNbCtrHbm];
+    route->tiers_run = launches;
+  }
+  return hipSuccess;
+}
+
+// ---- lattice prune (lattice_prune.hip holds the kernels) ----------------------------------
+
+hipError_t DeviceEngine::run_prune_batch(const LhsBatchDev& b, double beam, LatPruneDev p,
+                                         hipStream_t stream, LaunchStats* stats, LhsRoute* route) {
+  HIP_TRY(hipSetDevice(dev_));
+  const GraphInput& lhs = b.lhs;
+  const uint32_t num = b.in.num_strings;
+  if (stats) {
+    stats->engine = 15;
+    stats->grid = 0;
+    stats->launches = 0;
+  }
+  if (num == 0) return hipStreamSynchronize(stream);
+  uint32_t sweeps = 4;  // ids that rise along arcs settle in one or two; tests: FSTAMD_PRUNE_SWEEPS
+  if (const char* e = std::getenv("FSTAMD_PRUNE_SWEEPS"))
+    if (*e) sweeps = (uint32_t)std::min<unsigned long long>(std::strtoull(e, nullptr, 10), 1u << 20);
+  const uint32_t cap = grid_cap("FSTAMD_GRAPH_GRID");
+  const uint32_t cus = (uint32_t)std::max(num_cus_, 1);
+  const size_t ns = (size_t)b.total_states + 4, na = (size_t)b.total_arcs + 4;
+  p.desc = b.in.lhs_desc;
+  p.state_off = lhs.state_off;
+  p.final_w = lhs.final_w;
+  p.arc_next = lhs.arc_next;
+  p.arc_w = lhs.arc_w;
+  p.key = (unsigned long long*)scratch(kPrKey, 16 * ns);
+  p.list = (uint32_t*)scratch(kPrList, (size_t)num * 4);
+  p.ctr = (uint32_t*)scratch(kPrCtr, kPrCtrWords * 4);
+  if (!p.key || !p.list || !p.ctr) return hipErrorOutOfMemory;
+  p.beam = beam;
+  p.sweeps = sweeps;
+  p.wd_ticks = watchdog_ticks();
+  // every item starts as INTERNAL: an item no kernel finished can never read as a result
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p.status, kPathInternal, num, stream));
+  HIP_TRY(hipMemsetAsync(p.ctr, 0, kPrCtrWords * 4, stream));
+  uint32_t ctr[kPrCtrWords] = {};
+  uint32_t launches = 0, grid_max = 0;
+  HIP_TRY(timed(stats, stream, [&]() -> hipError_t {
+    grid_max = std::max<uint32_t>(1, std::min({num, cus * 32, cap}));
+    HIP_TRY(launch_prune_wave(p, num, grid_max, stream));
+    ++launches;
+    HIP_TRY(copy_sync(ctr, p.ctr, sizeof(ctr), hipMemcpyDeviceToHost, stream));
+    const uint32_t handed = ctr[kPrCtrList];
+    if (handed > num) return hipErrorUnknown;  // (the list holds an item at most once)
+    if (handed == 0) return hipSuccess;
+    // the frontier tier's words in one block: five per state, two per arc
+    uint32_t* w = (uint32_t*)scratch(kPrWork, 4 * (5 * ns + 2 * na));
+    if (!w) return hipErrorOutOfMemory;
+    p.mark = w;
+    p.fa = p.mark + ns;
+    p.fb = p.fa + ns;
+    p.roff = p.fb + ns;
+    p.rcur = p.roff + ns;
+    p.rsrc = p.rcur + ns;
+    p.rarc = p.rsrc + na;
+    const uint32_t g = std::max<uint32_t>(1, std::min({handed, cus * 8, cap}));
+    HIP_TRY(launch_prune_frontier(p, g, stream));
+    ++launches;
+    return copy_sync(ctr, p.ctr, sizeof(ctr), hipMemcpyDeviceToHost, stream);
+  }));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if ((uint64_t)ctr[kPrCtrWave] + ctr[kPrCtrFrontier] != num)
+    return hipErrorUnknown;  // (every item is finished by exactly one tier)
+  if (stats) {
+    stats->grid = grid_max;
+    stats->launches = launches;
+  }
+  if (route) {
+    *route = LhsRoute();
+    route->t[0] = ctr[kPrCtrWave];
+    route->t[1] = ctr[kPrCtrFrontier];
     route->tiers_run = launches;
   }
   return hipSuccess;

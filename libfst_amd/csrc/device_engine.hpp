@@ -330,6 +330,37 @@ struct LatSpDev {
   uint32_t n_best;
   unsigned long long wd_ticks;
 };
+// The lattice prune's inputs, workspace and outputs (kernels/lattice_prune.hpp):
+// the beam cut of every item of an lhs batch, the batch's CSR read in place.  The outputs are a
+// shadow view for the trim ladder: LatItem / status / start per item, the finals and the arcs'
+// targets with what the cut drops taken out (indexed like the batch's own arrays).
+enum : uint32_t { kPrCtrList = 0, kPrCtrWave = 1, kPrCtrFrontier = 2, kPrCtrWords = 4 };
+constexpr uint32_t kPruneLdsStates = 256;  // the wave tier keeps both key arrays in LDS up to here
+struct LatPruneDev {
+  const struct LhsDesc* desc;  // [num]
+  const uint32_t* state_off;   // the batch's arrays, as GraphInput holds them for a batch
+  const double* final_w;
+  const uint32_t* arc_next;
+  const double* arc_w;
+  unsigned long long* key;     // [2 * states] item at 2 * state_base: n keys of F, then n of B
+  uint32_t* mark;              // [states] the frontier tier: round stamps ...
+  uint32_t* fa;                // [states]     ... its two frontiers ...
+  uint32_t* fb;
+  uint32_t* roff;              // [states]     ... and the item's reverse CSR: offsets, cursors,
+  uint32_t* rcur;
+  uint32_t* rsrc;              // [arcs]       the arcs' sources and their indices
+  uint32_t* rarc;
+  uint32_t* list;              // [num] items the wave tier handed on
+  uint32_t* ctr;               // [kPrCtrWords] the list's length, items finished per tier
+  LatItem* item;               // [num] out
+  int32_t* status;             // [num] out
+  uint32_t* start;             // [num] out
+  double* sfin;                // [states] out: the kept final weights, +inf elsewhere
+  uint32_t* snext;             // [arcs] out: the kept arcs' targets, kNoState elsewhere
+  double beam;
+  uint32_t sweeps;             // the wave tier's budget per direction (FSTAMD_PRUNE_SWEEPS)
+  unsigned long long wd_ticks;
+};
 // The lattice n-best's inputs and workspace (kernels/lattice_nbest.hpp): the n
 // best distinct paths of every item of an lhs batch, the batch's CSR read in place.
 constexpr uint32_t kNbestMax = 16;  // FST_NBEST_MAX
@@ -565,6 +596,10 @@ hipError_t launch_sp_frontier(const LatSpDev& p, const BatchOutDev& out, uint32_
                               hipStream_t stream);
 hipError_t launch_sp_replay(const LatSpDev& p, const uint32_t* items, uint32_t count,
                             const BatchOutDev& out, uint32_t grid, hipStream_t stream);
+// ---- lattice prune (lattice_prune.hip, kernels/lattice_prune.hpp) ----
+hipError_t launch_prune_wave(const LatPruneDev& p, uint32_t num, uint32_t grid,
+                             hipStream_t stream);
+hipError_t launch_prune_frontier(const LatPruneDev& p, uint32_t grid, hipStream_t stream);
 // ---- input spans per output symbol (text_align.hip, kernels/text_align.hpp) ----
 hipError_t launch_align_write(const BatchOutDev& s, uint32_t num, const uint64_t* offsets,
                               uint32_t* begin, uint32_t* end, uint64_t cap, uint32_t* consumed,
@@ -764,6 +799,15 @@ class DeviceEngine {
   hipError_t run_nbest_batch(const LhsBatchDev& b, uint32_t n, bool unique,
                              const BatchOutDev& out, hipStream_t stream, LaunchStats* stats,
                              LhsRoute* route);
+  // The beam cut of every item of an lhs batch (fst_prune_lhs_batch; kernels/lattice_prune.hpp):
+  // forward and backward distances, then the mark pass into v's outputs (the caller's: item,
+  // status, start, sfin, snext; everything else of `v` is filled here, b's extents size the
+  // workspaces).  The wave tier takes every item and hands what its sweep budget
+  // (FSTAMD_PRUNE_SWEEPS) does not settle to the frontier tier.  The trim ladder on the shadow
+  // view is the caller's next step (host::prune_lattices).  route: t[0..1] = items the wave /
+  // frontier tier finished.  Synchronises `stream`.
+  hipError_t run_prune_batch(const LhsBatchDev& b, double beam, LatPruneDev v, hipStream_t stream,
+                             LaunchStats* stats, LhsRoute* route);
   // fst_compose_frozen: the whole lattice of one general lhs (kernels/eager_bfs.hpp), on
   // `stream` (synchronised: the lattice is downloaded).
   hipError_t compose_lattice(const DeviceFst& rhs, const GraphInput& lhs, HostLattice* lat,

@@ -311,6 +311,8 @@ FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n);
 FstError run_nbest_shard(Shard& S, const FstLhsBatch& L, uint32_t n, bool unique);
 // fst_connect_lhs_batch's shard: the items staged the same way, then trimmed.
 FstError run_connect_shard(Shard& S, const FstLhsBatch& L);
+// fst_prune_lhs_batch's shard: the items staged the same way, then prune_lattices.
+FstError run_prune_shard(Shard& S, const FstLhsBatch& L, double beam);
 // The compute steps of a lattice shard: chains from the caller's labels, or general lhs staged
 // as run_lhs_shard stages them; S.lat = the filled arena, S.keep = the statuses.
 FstError run_lattice_chain_shard(Shard& S, FrozenFst& b, const uint32_t* labels,
@@ -327,8 +329,17 @@ FstError run_lattice_arena(DeviceEngine::Lease& E, DeviceFst& D, const ChainInpu
 // tier for what it handed on, then the map and the trimmed counts in LatItem.  With
 // L.trim.start (the stand-alone entry) the accessibility pass runs first.  Adds its launches
 // and kernel time to t_last_stats; synchronises `stream`.
+// totals (optional): states before / after, arcs before / after.
 FstError trim_lattices(DeviceEngine::Lease& E, const int32_t* status, LatShard& L, uint32_t num,
-                       hipStream_t stream);
+                       hipStream_t stream, unsigned long long* totals = nullptr);
+// The beam cut and connect of every item of `b` (a batch in device memory: staged, or prepared
+// in place): DeviceEngine::run_prune_batch into a shadow arena (the batch's own arrays with the
+// cut's finals and targets), then trim_lattices on it.  *lat = that arena, ready for
+// compact_lattices with its trim; *keep = the statuses.  Sets t_last_stats (engine 15;
+// prep_launches: the caller's preparation kernels); synchronises `stream`.
+FstError prune_lattices(DeviceEngine::Lease& E, const LhsBatchDev& b, double beam,
+                        uint32_t prep_launches, hipStream_t stream,
+                        std::unique_ptr<LatShard>* lat, std::unique_ptr<DevOut>* keep);
 // run_sharded into a lattice result (fst_compose_frozen_batch): compact_lattices on the device,
 // both offset arrays rebased per shard.
 FstError run_sharded(const std::vector<int>& devices, uint32_t nsh, uint32_t num,

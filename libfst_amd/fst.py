@@ -175,6 +175,12 @@ SIGNATURES = {
     "fst_connect_lhs_batch": (
         C.c_int, [C.POINTER(FstLhsBatch), C.POINTER(FstBatchOptions),
                   C.POINTER(FstLatticeBatch)]),
+    "fst_prune_lhs_batch": (
+        C.c_int, [C.POINTER(FstLhsBatch), _f64, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstLatticeBatch)]),
+    "fst_device_prune_lhs": (
+        C.c_int, [C.POINTER(FstLhsBatch), _f64, C.POINTER(FstBatchOptions),
+                  C.POINTER(FstDeviceLattices), C.POINTER(_u64), _P]),
     "fst_shortest_path_lhs_batch": (
         C.c_int, [C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstBatchResult)]),
@@ -641,6 +647,21 @@ def connect_lhs_batch(lhs: LhsBatch, device: int = -1, devices=None,
     rc = lib().fst_connect_lhs_batch(C.byref(cs), C.byref(opts), C.byref(res))
     if rc != FST_OK:
         raise RuntimeError(f"fst_connect_lhs_batch failed: {rc}")
+    return LatticeBatch(res)
+
+
+def prune_lhs_batch(lhs: LhsBatch, beam: float, device: int = -1, devices=None,
+                    shards: int = 0) -> LatticeBatch:
+    """Beam pruning of every item of an lhs batch (fst_prune_lhs_batch): the arcs and final
+    weights on a complete path within `beam` of the item's best one, then connect.  Arc weights
+    must be >= 0 (an item with a negative or NaN weight is FST_PATH_UNSUPPORTED and empty);
+    beam = inf is connect on items of finite totals."""
+    opts = batch_options(device, FST_SEM_LAZY, devices, shards)
+    res = FstLatticeBatch()
+    cs = lhs.c_struct()
+    rc = lib().fst_prune_lhs_batch(C.byref(cs), float(beam), C.byref(opts), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_prune_lhs_batch failed: {rc}")
     return LatticeBatch(res)
 
 
