@@ -10,6 +10,7 @@
 
 #include "device_engine.hpp"
 #include "host_fst.hpp"
+#include "kernels/pull_window.hpp"
 #include "pull_kernel_dispatch.hpp"
 
 namespace fstamd {
@@ -245,8 +246,8 @@ bool build_reverse_mirror(DeviceFst* d, const FrozenFst& f) {
   };
   std::vector<uint32_t> rrec4;
   uint32_t rbias8 = 0;
+  int64_t dlo = 0, dhi = 0;  // the mirror's own jump range: every record's target - source
   if (!rrec8.empty() || widx) {
-    int64_t dlo = 0, dhi = 0;
     for (size_t r = 0; r < rrec.size(); ++r) {
       if (rrec[r].src == 0xFFFFFFF8u) continue;
       const int64_t dl = (int64_t)rtgt[r] - (int64_t)(rrec[r].src >> 3);
@@ -289,6 +290,12 @@ bool build_reverse_mirror(DeviceFst* d, const FrozenFst& f) {
   for (size_t g = 0; g < groups.size() && pack; ++g) pack = groups[g].label != 0xFFFFFFu;
   for (size_t r = 0; r < rrec4.size() && pack; ++r)
     pack = rrec4[r] == 0xFFFF0000u || (rrec4[r] >> 16) / 2 <= 252;
+  // ... and every source a window row can name must be a window cell or a guard cell
+  // (kernels/pull_window.hpp).  The kernel's windows follow RhsView's jumps, its records the
+  // mirror's dlo / dhi; both are taken over every arc in the device numbering and agree,
+  // but the bound is asked of the wider of the two
+  pack = pack && pack_guards_fit((uint32_t)std::max<int64_t>(d->view.jump_back, -dlo),
+                                 (uint32_t)std::max<int64_t>(d->view.jump_fwd, dhi), kPullW);
   if (pack) {
     const size_t n = rrec4.size();
     rrec4.resize(((n + 1) & ~(size_t)1) + n, 0xFFFF0000u);

@@ -46,6 +46,7 @@
 #include "eager_layered.hpp"  // EagerLaunch, write_status
 #include "eager_wave.hpp"     // wave_lds_sync, wave_pick_best
 #include "eager_window.hpp"   // ChaseJob, kChaseBatch
+#include "pull_window.hpp"    // the window rule, the packed cells' guard bands
 
 namespace fstamd {
 
@@ -115,14 +116,23 @@ struct PullLds<W, true> {
 // source) + rbias8 / 2, the byte distance between the two cells.  Padding slots of a block
 // repeat the block's first record with m = 15 (same candidate, larger key: never the back
 // key, never a new first key); blocks without any record hold 15 and are read only by rows
-// under the label-miss shift or by lanes the hub loop masks.
+// whose label misses or by lanes the hub loop masks.
+// Guard bands (pull_window.hpp, where the bound is derived): kPackGuardLo cells below the
+// window and kPackGuardHi above it hold kPackAbsent from the wave's start and are never
+// written again; window slot i is cell[kPackGuardLo + i].  Every source a row lane can name
+// -- outside the window, a block without records, every read of a label-miss row -- is a
+// window cell or a guard cell, so the cell's byte offset is base - delta4 as it stands: no
+// clamp per in-arc, no shifted origin for a miss.
 constexpr uint32_t kPackAbsent = 0x7F00FF80u;
 constexpr uint32_t kPackNoRank = 0xFF80u;  // low half of a candidate from an absent slot: >=
 constexpr uint32_t kPackPadM = 15u;
 template <int W>
 struct PullLdsPacked {
   static constexpr int kWords = W * 8 / 64;
-  uint32_t cell[W + 1];            // distance << 16 | rank << 7 (kPackAbsent: no tuple)
+  static constexpr int kCells = (int)pack_cells(W);
+  static_assert(pack_guards_fit(kPackSpanMax, 0, W) && pack_guards_fit(0, kPackSpanMax, W),
+                "packed cells: the guard bands hold every source of a window row");
+  uint32_t cell[kCells];           // distance << 16 | rank << 7 (kPackAbsent: no tuple)
   unsigned long long bits[kWords];
   uint4 pre[kWords];
   unsigned long long best;
@@ -325,10 +335,10 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
   const uint32_t lane = threadIdx.x;
   const DT kInf = PACK ? (DT)(kPackAbsent >> 16) : dist_inf<DT>();
   const uint32_t* const rpk = PACK ? rv_packed(rv) : nullptr;
-  // a cell: {distance, rank word}
+  // a cell: {distance, rank word} of window slot i
   auto set_cell = [&](uint32_t i, DT d, uint32_t rw) {
     if constexpr (PACK) {
-      S.cell[FB(i, W + 1, 153)] = ((uint32_t)d << 16) | rw;
+      S.cell[FB(kPackGuardLo + i, LdsT::kCells, 153)] = ((uint32_t)d << 16) | rw;
     } else if constexpr (F32) {
       S.cell[FB(i, W + 1, 153)] = make_uint2(d, rw);
     } else {
@@ -452,13 +462,20 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
     return w != 0u;
   };
 
+  if constexpr (PACK) {  // the window and both guard bands; the guards stay as they are here
+#pragma unroll 1
+    for (uint32_t i = lane; i < (uint32_t)LdsT::kCells; i += 64)
+      S.cell[FB(i, LdsT::kCells, 153)] = kPackAbsent;
+  } else {
 #pragma unroll 1
   for (uint32_t i = lane; i < (uint32_t)W + 1; i += 64) set_cell(i, kInf, kAbsent);
+  }
   if (lane < (uint32_t)kWords) S.bits[FB(lane, kWords, 157)] = 0;
   if constexpr (RK == 4 || RK == 5)
     for (uint32_t i = lane; i < (uint32_t)WT; i += 64) S.wt[i] = rv_weight_table(rv)[i];
   wave_lds_sync();
-  uint32_t wlast = 0;  // uniform: cells [wlast, W] hold no tuple
+  uint32_t wlast = 0;  // uniform: window cells [wlast, W) hold no tuple (nor does slot W of the
+                       // unpacked cells, nor any guard cell of the packed ones)
 
   for (;;) {
     uint32_t item = 0;
@@ -513,19 +530,20 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
       }
       // ---- window of the next layer: every target of a state in [cmin, cmax] lies in
       // [cmin - jump_back, cmax + jump_fwd] (RhsView) ----
-      const uint32_t tn = cmin >= rhs.jump_back ? cmin - rhs.jump_back : 0u;
+      // (the rule itself: pull_window.hpp)
+      const uint32_t tn = pull_win_tn(cmin, rhs.jump_back);
       // (32-bit: the pull tiers take rhs of fewer than 2^27 states, so cmax + jump_fwd
       // cannot wrap, and the compares stay scalar -- u64 ones went to the VALU)
-      const uint32_t hi = min(cmax + rhs.jump_fwd, rhs.num_states - 1);
+      const uint32_t hi = pull_win_hi(cmax, rhs.jump_fwd, rhs.num_states);
       const uint32_t nbase = base + wk;
       // (the slab's second half holds one header entry per layer: k < back_cap / 2)
-      if (hi - tn >= (uint32_t)W || nbase + (hi - tn + 1) > lp.back_cap ||
+      if (pull_win_overflow(tn, hi, (uint32_t)W) || nbase + pull_win_wn(tn, hi) > lp.back_cap ||
           k >= lp.back_cap / 2) {
         fail = kPathOverflow;  // the push tiers take the string
         break;
       }
-      const uint32_t wn = hi - tn + 1;
-      const uint32_t rows_n = (wn + 63) / 64;
+      const uint32_t wn = pull_win_wn(tn, hi);
+      const uint32_t rows_n = pull_win_rows(wn);
 
       // ---- (P1) pull: every target slot of the window merges its in-arcs ----
       uint32_t fst[EW], bk[EW], bra[EW];
@@ -560,8 +578,11 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
           // (packed cells: a block without records is no padding past every window, so the
           // row word of a state without in-arcs, 0xFFFFFF, must never hit; no rhs that has
           // packed records carries that in-label, eager_pull.hip)
+          // (packed cells with their guard bands: a miss takes a constant base instead,
+          // from which every read lands in the low guard)
           const bool hit = (rs & 0xFFFFFFu) == lab && lab < (PACK ? 0xFFFFFFu : kSpanMixed);
-          tmin8 = hit ? tmin8 : tmin8 + 0x80000000u;
+          if constexpr (PACK) tmin8 = hit ? pack_hit_base4(t, tmin, rv.rbias8 >> 1) : kPackMissBase4;
+          else tmin8 = hit ? tmin8 : tmin8 + 0x80000000u;
           rec0 = t * KP;
           nb = hit ? rs >> 24 : 0u;
         } else {
@@ -569,9 +590,9 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         }
         // RK 3: the records hold the source relative to the target, so the lane's base is
         // 8 * (t - window origin) + rbias8 (the 2^31 shift of a miss applies the same)
-        // packed cells: 4-B cells, base4 = 4 * (t - window origin) + rbias8 / 2
-        if constexpr (PACK) tmin8 = (t << 2) - (tmin << 2) + (rv.rbias8 >> 1) + (tmin8 - (tmin << 3));
-        else if constexpr (REC4) tmin8 = (t << 3) - (tmin << 3) + rv.rbias8 + (tmin8 - (tmin << 3));
+        // (packed cells: 4-B cells, base4 = 4 * (t - window origin + kPackGuardLo) + rbias8 / 2,
+        // set above)
+        if constexpr (REC4 && !PACK) tmin8 = (t << 3) - (tmin << 3) + rv.rbias8 + (tmin8 - (tmin << 3));
         if constexpr (!PACK) {
           // one base address, the records at immediate offsets
           const RT* R;
@@ -589,13 +610,14 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         DT b = kInf;
         uint32_t c = kEmptyKey;
         if constexpr (PACK) {
-          // per in-arc: the source's cell (one SDWA subtract, one min), the candidate (one
-          // mad), and its share of the two min trees (v_min3_u32 / v_min3_u16)
+          // per in-arc: the source's cell (one SDWA subtract; the guard bands make every
+          // such offset a legal one), the candidate (one mad), and its share of the two min
+          // trees (v_min3_u32 / v_min3_u16)
           // (the cells read in a loop of their own: the mads then wait for them once)
 #pragma unroll
           for (int m = 0; m < KP; ++m) {
-            const uint32_t off = min(tmin8 - (rr[m] >> 24), 4u * W);
-            rw[m] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(S.cell) + FB(off, 4 * (W + 1), 152));
+            const uint32_t off = pack_src_off4(tmin8, rr[m] >> 24);
+            rw[m] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(S.cell) + FB(off, 4 * LdsT::kCells, 152));
           }
 #pragma unroll
           for (int m = 0; m < KP; ++m) pk[m] = pack_candidate(rr[m], rw[m]);
@@ -662,8 +684,8 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
               if constexpr (PACK) {
                 // (an inactive lane's block holds no record: its candidate is dropped here)
                 const uint32_t r2 = rec(rx + m);
-                const uint32_t off = min(tmin8 - (r2 >> 24), 4u * W);
-                const uint32_t cl = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(S.cell) + FB(off, 4 * (W + 1), 152));
+                const uint32_t off = pack_src_off4(tmin8, r2 >> 24);
+                const uint32_t cl = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(S.cell) + FB(off, 4 * LdsT::kCells, 152));
                 const uint32_t p2 = pack_candidate(r2, cl);
                 if (act) {
                   f = min(f, p2 & 0xFFFFu);
@@ -749,7 +771,7 @@ eager_pull_kernel(RhsView rhs, RevView rv, ChainInput in, uint32_t n_best,
         // rank word alone marks it absent)
         // (packed cells: the merged word's distance half under the new rank)
         if constexpr (PACK)
-          S.cell[FB(i, W + 1, 153)] = (bk[e] & 0xFFFF0000u) | (pres ? rank << kRankShift : kAbsent);
+          S.cell[FB(kPackGuardLo + i, LdsT::kCells, 153)] = (bk[e] & 0xFFFF0000u) | (pres ? rank << kRankShift : kAbsent);
         else
           set_cell(i, bd[e], pres ? rank << kRankShift : kPullAbsent);
         const unsigned long long pm = __ballot(pres);
