@@ -561,6 +561,95 @@ FstError fst_prune_lhs_batch(const FstLhsBatch* lhs, double beam, const FstBatch
 FstError fst_device_prune_lhs(const FstLhsBatch* d_lhs, double beam, const FstBatchOptions* opts,
                               const FstDeviceLattices* out, uint64_t needed[2], void* stream);
 
+/* Arc posteriors of every item of an lhs batch, on the device: forward and backward sums in the
+ * LOG semiring (src/weight.zig:67-91, LogWeight.plus), the total mass of the lattice, and for
+ * every arc the share of that mass that runs through it, as -log.  The entries above work in the
+ * tropical semiring and say which readings are best; this one says how sure the lattice is of
+ * them (confidences beside alternatives, dropping low-confidence words, handing a lattice to a
+ * downstream model).  The reference has no such operation, so this comment is the definition.
+ *
+ * An item has states 0 .. S-1, arcs in CSR order (arc index a within the item), a start state,
+ * and src(a) -> dst(a) with weight w(a).  fl(.) is one rounding to f64.
+ * Statuses, tested in this order:
+ *   1. no start, or zero states: FST_PATH_EMPTY;
+ *   2. a NaN, or a -inf, arc or final weight anywhere in the item: FST_PATH_UNSUPPORTED;
+ *   3. a cycle among the states reachable from the start: FST_PATH_UNSUPPORTED
+ *      (fst_nbest_lhs_batch's rule: every arc counts, whatever its weight; a self-loop is a cycle);
+ *   4. device entry only: an item the prepare kernel refuses is FST_PATH_UNSUPPORTED;
+ *   5. any forward or backward value that comes out -inf (or NaN, which only sums of -inf give),
+ *      because finite weights overflowed: FST_PATH_UNSUPPORTED;
+ *   6. total == +inf, no complete path of finite cost: FST_PATH_EMPTY;
+ *   7. otherwise FST_PATH_OK.
+ * The sums.
+ *   logadd(x, y): if x == +inf return y; if y == +inf return x; otherwise, with m = min(x, y) and
+ *     d = max(x, y) - m, return m - log1p(exp(-d)).  These are the reference's plus, isZero and
+ *     times: a sum that is +inf is zero, an arc of weight +inf is never part of a path.
+ *   alpha(start) = 0.0.  For every other reachable t, alpha(t) is the fold
+ *     acc = +inf; acc = logadd(acc, fl(alpha(src(a)) + w(a)))
+ *     over the arcs a into t whose source is reachable, IN INCREASING ARC INDEX.
+ *     Unreachable states have alpha = +inf.
+ *   beta(s), for reachable s: acc = final(s) (+inf for a non-final state), then
+ *     acc = logadd(acc, fl(w(a) + beta(dst(a)))) over the arcs out of s IN INCREASING ARC INDEX.
+ *     Unreachable states have beta = +inf.
+ *   total = beta(start): -log Z, the log-sum over all complete paths.
+ *   arc_cost(a) = fl(fl(fl(alpha(src) + w(a)) + beta(dst)) - total), the arc's -log posterior;
+ *     +inf when any of the three terms is +inf.  It is not clamped: rounding may leave it a few
+ *     ulps below zero.
+ * Outputs, in the caller's own layout: alpha and beta are indexed like lhs->final_weights,
+ * arc_cost like lhs->weights; nothing is compacted.  Every entry of a non-OK item is +inf, and so
+ * is its total.
+ * The fold order is part of the contract: log-add is not associative in f64, and with a fixed
+ * order both tiers, every sharding and both entries give identical bytes.
+ * Error.  With u = 2^-53, D the number of levels (the longest path's states), d the largest in-
+ * or out-degree and M the largest finite magnitude among the weights, alpha and beta, every
+ * alpha, beta and total lies within D (d + 1) (M + 8) u of the value of the same fold in exact
+ * arithmetic, given exp and log1p within 2 ulp.
+ *
+ * Validation.  The same validator as every lhs entry: *out zeroed on error, a null lhs / out and
+ * unknown opts->flags rejected.  num_fsts == 0 gives the empty OK result.  opts->semantics is
+ * ignored.  The result lives in pooled pinned blocks until fst_posterior_result_free.
+ * FST_BATCH_DEVICES shards by arcs + 1 per item; a shard's state and arc ranges are written at
+ * the items' own offsets and a sharded result is byte-identical to a one-shard run.
+ * fst_last_launch_stats reports engine 16. */
+typedef struct {
+    uint32_t num_fsts;
+    int32_t* status;      /* [num_fsts] */
+    double*  total;       /* [num_fsts]  -log Z */
+    double*  alpha;       /* [total_states], as lhs->final_weights is indexed */
+    double*  beta;        /* [total_states] */
+    double*  arc_cost;    /* [total_arcs], as lhs->weights is indexed */
+    uint64_t total_states, total_arcs;
+} FstPosteriorResult;
+FstError fst_posterior_lhs_batch(const FstLhsBatch* lhs, const FstBatchOptions* opts,
+                                 FstPosteriorResult* out);
+void fst_posterior_result_free(FstPosteriorResult* r);
+
+/* Device-resident: d_lhs as for fst_device_shortest_path_lhs (a host struct of device pointers,
+ * trusted extents, per-item validation by the prepare kernel); out's arrays are device memory of
+ * the sizes above; alpha and beta may be NULL.  Only status and total are written for an item the
+ * prepare kernel refuses (its ranges cannot be trusted); if state_offsets decrease anywhere every
+ * item is FST_PATH_UNSUPPORTED and nothing else is written.  arc_cost lines up with d_lhs's
+ * weights, so chains -> fst_device_compose_frozen -> posteriors -> the caller's own kernel ->
+ * fst_device_prune_lhs or the n-best stays on the device.  The call SYNCHRONISES `stream`.
+ * Engine 16; `launches` counts the preparation kernels too. */
+typedef struct {
+    int32_t* status;      /* [num_fsts] */
+    double*  total;       /* [num_fsts] */
+    double*  alpha;       /* [total_states], or NULL */
+    double*  beta;        /* [total_states], or NULL */
+    double*  arc_cost;    /* [total_arcs] */
+} FstDevicePosteriors;
+FstError fst_device_posterior_lhs(const FstLhsBatch* d_lhs, const FstBatchOptions* opts,
+                                  const FstDevicePosteriors* out, void* stream);
+
+/* -log confidences of n-best paths (host only, no GPU): `paths` holds `per` strings per item
+ * (fst_nbest_lhs_batch's result at n = per), total[i] is item i's -log Z.  For an OK string,
+ * out[i * per + k] = fl(fl(c + final_weight) - total[i]) with c the left fold of the path's
+ * weights from 0.0; +inf for every other string.  FST_INVALID_ARG for a null argument,
+ * per == 0, or paths->num_strings != num_fsts * per. */
+FstError fst_batch_result_path_costs(const FstBatchResult* paths, uint32_t per,
+                                     const double* total, uint32_t num_fsts, double* out);
+
 /* Text in, text out: the loop the reference application runs per utterance and stage,
  *   fst_compile_string(bytes) -> fst_compose_frozen_shortest_path -> fst_print_output_string
  * (README.md:177-214, src/string.zig:17-97), for a whole batch with bytes on both sides of
@@ -748,7 +837,10 @@ typedef struct {
                                         a text hash per list entry),
                                    15 = fst_prune_lhs_batch and fst_device_prune_lhs (one wave
                                         per lattice for both distances and the cut, a workgroup
-                                        per lattice behind it, then the trim kernels) */
+                                        per lattice behind it, then the trim kernels),
+                                   16 = fst_posterior_lhs_batch and fst_device_posterior_lhs
+                                        (one wave per lattice with its tables in LDS, a workgroup
+                                        per lattice with them in HBM behind it) */
     uint32_t grid;              /* workgroups of the dominant kernel */
 } FstLaunchStats;
 FstError fst_last_launch_stats(FstLaunchStats* out);

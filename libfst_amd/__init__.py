@@ -17,4 +17,6 @@ from .fst import (  # noqa: F401
     FST_LATTICE_CONNECT, connect_lhs_batch, shortest_path_lhs_batch,
     AlignedTextResult, FstAlignedTextResult, batch_result_to_aligned_text,
     normalize_text_aligned_batch, FST_NBEST_MAX, nbest_lhs_batch,
-    nbest_unique_lhs_batch, prune_lhs_batch)
+    nbest_unique_lhs_batch, prune_lhs_batch,
+    FstDevicePosteriors, FstPosteriorResult, PosteriorResult, batch_result_path_costs,
+    posterior_lhs_batch)

@@ -1,7 +1,11 @@
 // batch_entries.cpp -- the fst_batch.h C ABI: argument checks, the choice of route (streamed,
 // pipelined, sharded), the device-side entries.  (fst_debug_coalescer_state: c_api.cpp.)
 
+#include <algorithm>
+#include <cmath>
+
 #include "host_rt.hpp"
+#include "posterior_gather.hpp"
 #include "weight_codes.hpp"
 
 using namespace fstamd;
@@ -557,6 +561,94 @@ FstError fst_nbest_unique_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
   return nbest_lhs_entry(lhs, n, true, opts, out, "fst_nbest_unique_lhs_batch");
 }
 
+// Arc posteriors of every item of an lhs batch: staged as above (run_posterior_shard).  The
+// result is in the caller's own layout, so nothing is compacted: a shard's totals are its items'
+// states and arcs, and its download puts the three value arrays at the offsets of its first item
+// (posterior_gather.hpp, checked on its own by tools/posterior_gather_check.cpp).
+FstError fst_posterior_lhs_batch(const FstLhsBatch* lhs, const FstBatchOptions* opts,
+                                 FstPosteriorResult* out) {
+  if (!out) return FST_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));
+  if (!lhs_batch_valid(lhs) || !flags_ok(opts)) return FST_INVALID_ARG;
+  const uint32_t num = lhs->num_fsts;
+  const uint64_t states = num ? lhs->state_offsets[num] : 0;
+  const uint64_t arcs = num ? lhs->arc_offsets[states] : 0;
+  const auto alloc = [=](uint64_t, uint64_t) {
+    out->num_fsts = num;
+    out->total_states = states;
+    out->total_arcs = arcs;
+    out->status = (int32_t*)pin_alloc(std::max<size_t>(num, 1) * 4);
+    out->total = (double*)pin_alloc(std::max<size_t>(num, 1) * 8);
+    out->alpha = (double*)pin_alloc(std::max<uint64_t>(states, 1) * 8);
+    out->beta = (double*)pin_alloc(std::max<uint64_t>(states, 1) * 8);
+    out->arc_cost = (double*)pin_alloc(std::max<uint64_t>(arcs, 1) * 8);
+    if (!out->status || !out->total || !out->alpha || !out->beta || !out->arc_cost) return false;
+    posterior_fill_front(lhs->state_offsets, lhs->arc_offsets, num, out->alpha, out->beta,
+                         out->arc_cost);
+    return true;
+  };
+  if (num == 0) {
+    if (alloc(0, 0)) return FST_OK;
+    fst_posterior_result_free(out);
+    return FST_OOM;
+  }
+  BatchCall call;
+  if (FstError e = call.open(opts); e != FST_OK) return e;
+  const ShardSink sink{
+      [](Shard&) { return FST_OK; }, alloc,
+      [=](Shard& S, uint64_t, uint64_t) {
+        const hipStream_t stream = S.E.stream();
+        const PosteriorRanges r =
+            posterior_shard_ranges(lhs->state_offsets, lhs->arc_offsets, S.s0, S.s1);
+        if (r.ns != S.tot || r.na != S.tot2) return FST_OOM;  // (a bug: the shard staged these)
+        const auto copy = [&](void* dst, const void* src, uint64_t bytes) {
+          return d2h(dst, src, bytes, stream);
+        };
+        return posterior_gather_shard(r, S.s0, S.s1, (const int32_t*)S.keep->status.p,
+                                      (const double*)S.keep->fin.p, (const double*)S.w->p,
+                                      out->status, out->total, out->alpha, out->beta,
+                                      out->arc_cost, copy) &&
+                       hipStreamSynchronize(stream) == hipSuccess
+                   ? FST_OK
+                   : FST_OOM;
+      },
+      [](uint64_t, uint64_t) {}};
+  const FstError e = run_sharded(
+      call.devices, call.nsh, num, lhs_costs(*lhs, call.nsh),
+      [&](Shard& S) { return run_posterior_shard(S, *lhs); }, sink);
+  return call.close(e, "fst_posterior_lhs_batch", out, fst_posterior_result_free);
+}
+
+void fst_posterior_result_free(FstPosteriorResult* r) {
+  if (!r) return;
+  pin_release(r->status);
+  pin_release(r->total);
+  pin_release(r->alpha);
+  pin_release(r->beta);
+  pin_release(r->arc_cost);
+  std::memset(r, 0, sizeof(*r));
+}
+
+// -log confidences of the strings of an n-best result: host arithmetic alone, no GPU.
+FstError fst_batch_result_path_costs(const FstBatchResult* paths, uint32_t per,
+                                     const double* total, uint32_t num_fsts, double* out) {
+  if (!paths || !total || !out || per == 0 || (uint64_t)num_fsts * per != paths->num_strings)
+    return FST_INVALID_ARG;
+  for (uint32_t i = 0; i < num_fsts; ++i)
+    for (uint32_t k = 0; k < per; ++k) {
+      const uint64_t s = (uint64_t)i * per + k;
+      double c = HUGE_VAL;
+      if (paths->status[s] == FST_PATH_OK) {
+        c = 0.0;
+        for (uint64_t a = paths->path_offsets[s]; a < paths->path_offsets[s + 1]; ++a)
+          c = c + paths->weights[a];
+        c = (c + paths->final_weights[s]) - total[i];
+      }
+      out[s] = c;
+    }
+  return FST_OK;
+}
+
 void fst_lattice_batch_free(FstLatticeBatch* r) {
   if (!r) return;
   pin_release(r->status);
@@ -754,6 +846,40 @@ FstError fst_device_nbest_unique_lhs(const FstLhsBatch* d_lhs, uint32_t n,
                                      const FstBatchOptions* opts, const FstDeviceBatch* o,
                                      void* stream) {
   return device_nbest_entry(d_lhs, n, true, opts, o, stream);
+}
+
+// Arc posteriors of a device-resident lhs batch: prepared like the shortest path's, then
+// DeviceEngine::run_posterior_batch straight into the caller's arrays, which are indexed by the
+// items' own (global) bases.
+FstError fst_device_posterior_lhs(const FstLhsBatch* d_lhs, const FstBatchOptions* opts,
+                                  const FstDevicePosteriors* o, void* stream) {
+  if (!device_lhs_args_ok(d_lhs) || !o || !flags_ok(opts)) return FST_INVALID_ARG;
+  const uint32_t num = d_lhs->num_fsts;
+  if (num && (!o->status || !o->total)) return FST_INVALID_ARG;
+  DeviceCall call;
+  if (FstError e = call.open(opts, nullptr, stream); e != FST_OK) return e;
+  LaunchStats st;
+  st.engine = 16;
+  if (num == 0) {
+    t_last_stats = st;
+    call.drain.done = true;  // (nothing was queued)
+    return FST_OK;
+  }
+  LhsBatchDev batch;
+  LhsPrepared p;
+  if (FstError e = device_lhs_prepare(call, d_lhs, &batch, &p); e != FST_OK) return e;
+  if (batch.total_arcs && !o->arc_cost) return FST_INVALID_ARG;
+  LatPostDev v{};
+  v.status = o->status;
+  v.total = o->total;
+  v.alpha = o->alpha;
+  v.beta = o->beta;
+  v.arc_cost = o->arc_cost;
+  if (call.E->run_posterior_batch(batch, v, call.s, &st, nullptr) != hipSuccess) return FST_OOM;
+  st.launches += p.launches;
+  t_last_stats = st;
+  call.drain.done = true;  // (run_posterior_batch synchronised the stream)
+  return FST_OK;
 }
 
 FstError fst_device_project_output(const FstDeviceBatch* o, uint32_t num_strings,

@@ -1,6 +1,7 @@
 // batch_lhs.cpp -- host batches of general lhs (lattices, confusion networks) and the lattice
 // batch: the staging of a shard's items into one block (stage_lhs_items), the shard steps on it
-// (1-best, pipelines on a general first stage, shortest path, n-best, connect, prune), the lattice
+// (1-best, pipelines on a general first stage, shortest path, n-best, posteriors, connect, prune),
+// the lattice
 // arena with its reruns, the trim and prune drivers, the two lattice shard steps, and the lattice
 // sink of run_sharded.
 // run_arena, run_sharded itself and the chain stages: batch_sharded.cpp.
@@ -182,6 +183,48 @@ FstError run_nbest_shard(Shard& S, const FstLhsBatch& L, uint32_t n, bool unique
       [&](const LhsBatchDev& b, const BatchOutDev& v, hipStream_t stream, LaunchStats* ls) {
         return S.E->run_nbest_batch(b, n, unique, v, stream, ls, nullptr);
       });
+}
+
+// One shard of fst_posterior_lhs_batch: the staged items through
+// DeviceEngine::run_posterior_batch, which reads the staged block in place and synchronises the
+// stream.  S.keep holds the statuses and, as its final weights, the totals; S.w the shard's
+// alpha, beta (S.tot states each) and arc costs (S.tot2 arcs), in the shard's own order.
+FstError run_posterior_shard(Shard& S, const FstLhsBatch& L) {
+  const int dev = S.E->dev();
+  if (hipSetDevice(dev) != hipSuccess) return FST_INVALID_ARG;
+  const hipStream_t stream = S.E.stream();
+  const uint32_t num = S.s1 - S.s0;
+  LhsStaged st;
+  // every return drains the stream before the staged blocks and the outputs go back to their pools
+  StreamDrain drain{{stream}};
+  if (FstError e = stage_lhs_items(S, nullptr, L, stream, &st); e != FST_OK) return e;
+  const uint64_t ns = st.b.total_states, na = st.b.total_arcs;
+  auto out = std::make_unique<DevOut>(num, 1);
+  auto vals = std::make_unique<DevBuf>((2 * ns + na + 2) * 8);
+  if (!out->ok() || !vals->p) return FST_OOM;
+  if (t_prof) t_prof->lap(1);
+  LatPostDev v{};
+  v.status = out->v.status;
+  v.total = out->v.final_w;
+  v.alpha = (double*)vals->p;
+  v.beta = v.alpha + ns;
+  v.arc_cost = v.beta + ns;
+  LaunchStats ls;
+  const hipError_t err = S.E->run_posterior_batch(st.b, v, stream, &ls, nullptr);
+  if (t_prof) {
+    t_prof->lap(2);
+    ++t_prof->runs;
+  }
+  if (err != hipSuccess) {
+    std::fprintf(stderr, "[libfst_amd] lattice posterior failed: %s\n", hipGetErrorString(err));
+    return FST_OOM;
+  }
+  t_last_stats = ls;
+  S.keep = std::move(out);
+  S.w = std::move(vals);
+  S.tot = ns;
+  S.tot2 = na;
+  return FST_OK;  // (the drain: the engine synchronised, nothing is left to wait for)
 }
 
 // ---- Lattice shards ---------------------------------------------------------------------

@@ -476,6 +476,9 @@ enum Scratch : size_t {
   kPrWork,
   kPrList,
   kPrCtr,
+  kPostWork,
+  kPostList,
+  kPostCtr,
   kNumScratch
 };
 
@@ -3302,6 +3305,96 @@ hipError_t DeviceEngine::run_prune_batch(const LhsBatchDev& b, double beam, LatP
     *route = LhsRoute();
     route->t[0] = ctr[kPrCtrWave];
     route->t[1] = ctr[kPrCtrFrontier];
+    route->tiers_run = launches;
+  }
+  return hipSuccess;
+}
+
+// ---- lattice posteriors (lattice_posterior.hip holds the kernels) -------------------------
+
+hipError_t DeviceEngine::run_posterior_batch(const LhsBatchDev& b, LatPostDev v,
+                                             hipStream_t stream, LaunchStats* stats,
+                                             LhsRoute* route) {
+  HIP_TRY(hipSetDevice(dev_));
+  const GraphInput& lhs = b.lhs;
+  const uint32_t num = b.in.num_strings;
+  if (stats) {
+    stats->engine = 16;
+    stats->grid = 0;
+    stats->launches = 0;
+  }
+  if (num == 0) return hipStreamSynchronize(stream);
+  // The wave tier's budget per workgroup (one wave): 8 KiB, the best of a sweep from 4 to 60 KiB
+  // on the tagger stand-in's lattices (it holds an item of 128 states and 512
+  // arcs and leaves 18 waves to a CU; a larger one costs residency faster than it saves
+  // workgroup-tier items).  Tests move it: FSTAMD_POSTERIOR_LDS bytes, 0 sends every item to the
+  // workgroup tier.
+  uint32_t budget = 8192;
+  if (const char* e = std::getenv("FSTAMD_POSTERIOR_LDS"))
+    if (*e) budget = (uint32_t)std::min<unsigned long long>(std::strtoull(e, nullptr, 10), 61440);
+  budget &= ~15u;
+  const uint32_t cap = grid_cap("FSTAMD_GRAPH_GRID");
+  const uint32_t cus = (uint32_t)std::max(num_cus_, 1);
+  LatNbestDev& p = v.nb;
+  p = LatNbestDev{};
+  p.desc = b.in.lhs_desc;
+  p.state_off = lhs.state_off;
+  p.final_w = lhs.final_w;
+  p.arc_next = lhs.arc_next;
+  p.arc_il = lhs.arc_il;
+  p.arc_ol = lhs.arc_ol;
+  p.arc_w = lhs.arc_w;
+  p.list = (uint32_t*)scratch(kPostList, (size_t)num * 4);
+  p.ctr = (uint32_t*)scratch(kPostCtr, kNbCtrWords * 4);
+  if (!p.list || !p.ctr) return hipErrorOutOfMemory;
+  p.lds_budget = budget;
+  p.wd_ticks = watchdog_ticks();
+  // every item starts as INTERNAL: an item no kernel finished can never read as a result
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)v.status, kPathInternal, num, stream));
+  HIP_TRY(hipMemsetAsync(p.ctr, 0, kNbCtrWords * 4, stream));
+  uint32_t ctr[kNbCtrWords] = {};
+  uint32_t launches = 0, grid_max = 0;
+  HIP_TRY(timed(stats, stream, [&]() -> hipError_t {
+    const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(32, 163840 / (budget + 512)));
+    grid_max = std::max<uint32_t>(1, std::min({num, cus * per_cu, cap}));
+    HIP_TRY(launch_posterior_lds(v, num, grid_max, stream));
+    ++launches;
+    HIP_TRY(copy_sync(ctr, p.ctr, sizeof(ctr), hipMemcpyDeviceToHost, stream));
+    const uint32_t handed = ctr[kNbCtrList];
+    if (handed > num) return hipErrorUnknown;  // (the list holds an item at most once)
+    if (handed == 0) return hipSuccess;
+    // the workgroup tier's tables in one block: 32 B per state, 8 B per arc
+    const size_t ns = (size_t)b.total_states + 4, na = (size_t)b.total_arcs + 4;
+    uint8_t* w = (uint8_t*)scratch(kPostWork, 32 * ns + 8 * na);
+    if (!w) return hipErrorOutOfMemory;
+    p.eg = (unsigned long long*)w;
+    p.ear = p.eg + ns;
+    p.depth = (uint32_t*)(p.ear + ns);
+    p.roff = p.depth + ns;
+    p.lvl = p.roff + ns;
+    p.order = p.lvl + ns;
+    p.rarc = p.order + ns;
+    p.asrc = p.rarc + na;
+    const uint32_t g = std::max<uint32_t>(1, std::min({handed, cus * 8, cap}));
+    HIP_TRY(launch_posterior_hbm(v, g, stream));
+    grid_max = std::max(grid_max, g);
+    ++launches;
+    return copy_sync(ctr, p.ctr, sizeof(ctr), hipMemcpyDeviceToHost, stream);
+  }));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if ((uint64_t)ctr[kNbCtrLds] + ctr[kNbCtrHbm] != num)
+    return hipErrorUnknown;  // (every item is finished by exactly one tier)
+  if (stats) {
+    stats->grid = grid_max;
+    stats->launches = launches;
+  }
+  if (std::getenv("FSTAMD_ROUTE_LOG"))
+    std::fprintf(stderr, "[libfst_amd route] lattice posterior: items %u | lds %u hbm %u | %.3f ms\n",
+                 num, ctr[kNbCtrLds], ctr[kNbCtrHbm], stats ? stats->kernel_ms : 0.0);
+  if (route) {
+    *route = LhsRoute();
+    route->t[0] = ctr[kNbCtrLds];
+    route->t[1] = ctr[kNbCtrHbm];
     route->tiers_run = launches;
   }
   return hipSuccess;

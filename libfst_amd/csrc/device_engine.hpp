@@ -392,6 +392,19 @@ struct LatNbestDev {
   unsigned long long* eh;      // [states * n] the HBM tier's text hashes, beside eg and ear
   unsigned long long hash_mask;  // ANDed onto every hash (FSTAMD_NBEST_HASH_MASK; all ones)
 };
+// The lattice posteriors' inputs, workspace and outputs (kernels/lattice_posterior.hpp, DESIGN.md
+// §7l).  `nb` is the n-best's view of the batch (nb_item reads it), its list and counters, and
+// the workgroup tier's tables: eg / ear hold alpha / beta (8 B per state), depth, roff, lvl,
+// order and rarc, asrc as there; cnt, eh, n_best and hash_mask are not used.  The outputs are
+// indexed by the items' own bases: alpha, beta like final_w, arc_cost like arc_w.
+struct LatPostDev {
+  LatNbestDev nb;
+  int32_t* status;   // [num] out
+  double* total;     // [num] out: -log Z, +inf unless OK
+  double* alpha;     // [states] out, or null
+  double* beta;      // [states] out, or null
+  double* arc_cost;  // [arcs] out
+};
 
 // Chain inputs (batch API) or one general lhs FST (single-call C ABI).
 struct ChainInput {
@@ -615,6 +628,10 @@ hipError_t launch_nbest_lds(const LatNbestDev& p, bool unique, uint32_t count,
                             const BatchOutDev& out, uint32_t grid, hipStream_t stream);
 hipError_t launch_nbest_hbm(const LatNbestDev& p, bool unique, const BatchOutDev& out,
                             uint32_t grid, hipStream_t stream);
+// ---- lattice posteriors (lattice_posterior.hip, kernels/lattice_posterior.hpp) ----
+hipError_t launch_posterior_lds(const LatPostDev& p, uint32_t count, uint32_t grid,
+                                hipStream_t stream);
+hipError_t launch_posterior_hbm(const LatPostDev& p, uint32_t grid, hipStream_t stream);
 // On-device preparation of a device-resident batch (kernels/lhs_prepare.hpp; lhs_batch.hip
 // holds the instances).  In: the caller's arrays in FstLhsBatch's layout, all device memory,
 // and their two extents as the host read them.  Out: descriptors, local arc offsets
@@ -808,6 +825,15 @@ class DeviceEngine {
   // frontier tier finished.  Synchronises `stream`.
   hipError_t run_prune_batch(const LhsBatchDev& b, double beam, LatPruneDev v, hipStream_t stream,
                              LaunchStats* stats, LhsRoute* route);
+  // Arc posteriors of every item of an lhs batch (fst_posterior_lhs_batch; kernels/
+  // lattice_posterior.hpp): v's outputs are the caller's (status, total, alpha, beta, arc_cost;
+  // alpha and beta may be null), everything else of `v` is filled here.  The wave tier (one wave
+  // per item, a budget of 8 KiB of LDS per workgroup, or FSTAMD_POSTERIOR_LDS bytes; 0: no item
+  // fits) hands the items whose tables do not fit to the workgroup tier, whose workspace b's
+  // extents size (it is allocated only when an item needs it).  route: t[0..1] = items the wave /
+  // workgroup tier finished.  Synchronises `stream`.
+  hipError_t run_posterior_batch(const LhsBatchDev& b, LatPostDev v, hipStream_t stream,
+                                 LaunchStats* stats, LhsRoute* route);
   // fst_compose_frozen: the whole lattice of one general lhs (kernels/eager_bfs.hpp), on
   // `stream` (synchronised: the lattice is downloaded).
   hipError_t compose_lattice(const DeviceFst& rhs, const GraphInput& lhs, HostLattice* lat,

@@ -309,6 +309,10 @@ FstError run_sp_shard(Shard& S, const FstLhsBatch& L, uint32_t n);
 // strings per item and a path arena of n times the shard's states; S.keep = the paths.
 // unique: fst_nbest_unique_lhs_batch's (one path per output text).
 FstError run_nbest_shard(Shard& S, const FstLhsBatch& L, uint32_t n, bool unique);
+// fst_posterior_lhs_batch's shard: the same staging, then DeviceEngine::run_posterior_batch;
+// S.keep = the statuses and totals, S.w = alpha, beta and the arc costs, S.tot / S.tot2 = the
+// shard's states / arcs.
+FstError run_posterior_shard(Shard& S, const FstLhsBatch& L);
 // fst_connect_lhs_batch's shard: the items staged the same way, then trimmed.
 FstError run_connect_shard(Shard& S, const FstLhsBatch& L);
 // fst_prune_lhs_batch's shard: the items staged the same way, then prune_lattices.

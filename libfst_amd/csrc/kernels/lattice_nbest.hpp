@@ -612,6 +612,9 @@ __device__ __forceinline__ void nb_lds_tier(const LatNbestDev& p, uint32_t count
   if (threadIdx.x == 0 && done) atomicAdd(&p.ctr[kNbCtrLds], done);
 }
 
+// (FSTAMD_NBEST_NO_KERNELS: a unit that includes this header for its helpers alone, as
+// lattice_posterior.hpp does, defines it so that the kernels stay lattice_nbest.hip's)
+#ifndef FSTAMD_NBEST_NO_KERNELS
 __global__ void __launch_bounds__(64)
 lattice_nbest_lds_kernel(LatNbestDev p, uint32_t count, BatchOutDev out) {
   extern __shared__ __align__(16) unsigned char nb_lds[];
@@ -625,6 +628,7 @@ lattice_nbest_unique_lds_kernel(LatNbestDev p, uint32_t count, BatchOutDev out) 
   __shared__ NbSharedUnique SH;
   nb_lds_tier<true>(p, count, out, nb_lds, SH);
 }
+#endif
 
 // ---- HBM tier: one workgroup per listed item, the tables in the workspace -----------------
 // The item's slices: list entries at state_base * n, state words at state_base, arc words at
@@ -657,6 +661,7 @@ __device__ __forceinline__ void nb_hbm_tier(const LatNbestDev& p, const BatchOut
   }
 }
 
+#ifndef FSTAMD_NBEST_NO_KERNELS
 __global__ void __launch_bounds__(kNbWG)
 lattice_nbest_hbm_kernel(LatNbestDev p, BatchOutDev out) {
   __shared__ NbShared SH;
@@ -668,5 +673,6 @@ lattice_nbest_unique_hbm_kernel(LatNbestDev p, BatchOutDev out) {
   __shared__ NbSharedUnique SH;
   nb_hbm_tier<true>(p, out, SH);
 }
+#endif
 
 }  // namespace fstamd

@@ -106,6 +106,18 @@ class FstDeviceLattices(C.Structure):
                 ("arc_capacity", C.c_uint64)]
 
 
+class FstPosteriorResult(C.Structure):
+    _fields_ = [("num_fsts", C.c_uint32), ("status", C.POINTER(C.c_int32)),
+                ("total", C.POINTER(C.c_double)), ("alpha", C.POINTER(C.c_double)),
+                ("beta", C.POINTER(C.c_double)), ("arc_cost", C.POINTER(C.c_double)),
+                ("total_states", C.c_uint64), ("total_arcs", C.c_uint64)]
+
+
+class FstDevicePosteriors(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("total", C.c_void_p), ("alpha", C.c_void_p),
+                ("beta", C.c_void_p), ("arc_cost", C.c_void_p)]
+
+
 class FstLaunchStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("launches", C.c_uint32), ("engine", C.c_uint32),
                 ("grid", C.c_uint32)]
@@ -181,6 +193,14 @@ SIGNATURES = {
     "fst_device_prune_lhs": (
         C.c_int, [C.POINTER(FstLhsBatch), _f64, C.POINTER(FstBatchOptions),
                   C.POINTER(FstDeviceLattices), C.POINTER(_u64), _P]),
+    "fst_posterior_lhs_batch": (
+        C.c_int, [C.POINTER(FstLhsBatch), C.POINTER(FstBatchOptions),
+                  C.POINTER(FstPosteriorResult)]),
+    "fst_posterior_result_free": (None, [C.POINTER(FstPosteriorResult)]),
+    "fst_device_posterior_lhs": (
+        C.c_int, [C.POINTER(FstLhsBatch), C.POINTER(FstBatchOptions),
+                  C.POINTER(FstDevicePosteriors), _P]),
+    "fst_batch_result_path_costs": (C.c_int, [C.POINTER(FstBatchResult), _u32, _P, _u32, _P]),
     "fst_shortest_path_lhs_batch": (
         C.c_int, [C.POINTER(FstLhsBatch), _u32, C.POINTER(FstBatchOptions),
                   C.POINTER(FstBatchResult)]),
@@ -663,6 +683,88 @@ def prune_lhs_batch(lhs: LhsBatch, beam: float, device: int = -1, devices=None,
     if rc != FST_OK:
         raise RuntimeError(f"fst_prune_lhs_batch failed: {rc}")
     return LatticeBatch(res)
+
+
+class _PosteriorOwner:
+    """Owns one FstPosteriorResult; fst_posterior_result_free runs once no array views it."""
+
+    def __init__(self, res):
+        self.res = res
+
+    def __del__(self):
+        try:
+            lib().fst_posterior_result_free(C.byref(self.res))
+        except Exception:  # interpreter shutdown
+            pass
+
+
+class PosteriorResult:
+    """The result of posterior_lhs_batch, as numpy views of the library's pinned arrays (no copy;
+    the arrays keep the result alive): `status` and `total` (-log Z) per item, `alpha` and `beta`
+    indexed like the batch's final_weights, `arc_cost` (the arc's -log posterior) like its
+    weights.  Every entry of a non-OK item is +inf."""
+
+    def __init__(self, res: FstPosteriorResult):
+        num, ns, na = int(res.num_fsts), int(res.total_states), int(res.total_arcs)
+        owner = _PosteriorOwner(res)
+        self._owner = owner
+
+        def arr(p, cnt, dt, ct):
+            if cnt == 0:
+                return np.zeros(0, dt)
+            buf = (ct * cnt).from_address(C.cast(p, C.c_void_p).value)
+            buf._owner = owner  # the view keeps the result alive
+            return np.frombuffer(buf, dtype=dt)
+
+        self.status = arr(res.status, num, np.int32, C.c_int32)
+        self.total = arr(res.total, num, np.float64, C.c_double)
+        self.alpha = arr(res.alpha, ns, np.float64, C.c_double)
+        self.beta = arr(res.beta, ns, np.float64, C.c_double)
+        self.arc_cost = arr(res.arc_cost, na, np.float64, C.c_double)
+
+    def __len__(self):
+        return len(self.status)
+
+
+def posterior_lhs_batch(lhs: LhsBatch, device: int = -1, devices=None,
+                        shards: int = 0) -> PosteriorResult:
+    """Arc posteriors of every item of an lhs batch of acyclic items (fst_posterior_lhs_batch;
+    the sums and their order are defined in fst_batch.h): forward and backward log-semiring
+    sums, the total mass and every arc's -log posterior, in the batch's own layout."""
+    opts = batch_options(device, FST_SEM_LAZY, devices, shards)
+    res = FstPosteriorResult()
+    cs = lhs.c_struct()
+    rc = lib().fst_posterior_lhs_batch(C.byref(cs), C.byref(opts), C.byref(res))
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_posterior_lhs_batch failed: {rc}")
+    return PosteriorResult(res)
+
+
+def batch_result_path_costs(result: "BatchResult", per: int, total) -> np.ndarray:
+    """-log confidences of an n-best result (fst_batch_result_path_costs): `result` holds `per`
+    strings per item, total[i] is item i's -log Z (PosteriorResult.total); out[i * per + k] is
+    the k-th path's cost minus the total, +inf for a string that is not OK.  Runs without a GPU."""
+    status = np.ascontiguousarray(result.status, dtype=np.int32)
+    offsets = np.ascontiguousarray(result.offsets, dtype=np.uint64)
+    ilabels = np.ascontiguousarray(result.ilabels, dtype=np.uint32)
+    olabels = np.ascontiguousarray(result.olabels, dtype=np.uint32)
+    weights = np.ascontiguousarray(result.weights, dtype=np.float64)
+    finals = np.ascontiguousarray(result.finals, dtype=np.float64)
+    total = np.ascontiguousarray(total, dtype=np.float64)
+
+    def ptr(a, ct):
+        return C.cast(a.ctypes.data, C.POINTER(ct))
+
+    src = FstBatchResult(len(status), ptr(status, C.c_int32), ptr(offsets, C.c_uint64),
+                         ptr(ilabels, C.c_uint32), ptr(olabels, C.c_uint32),
+                         ptr(weights, C.c_double), ptr(finals, C.c_double),
+                         int(offsets[-1]) if len(offsets) else 0)
+    out = np.empty(max(len(status), 1), dtype=np.float64)
+    rc = lib().fst_batch_result_path_costs(C.byref(src), int(per), total.ctypes.data, len(total),
+                                           out.ctypes.data)
+    if rc != FST_OK:
+        raise RuntimeError(f"fst_batch_result_path_costs failed: {rc}")
+    return out[:len(status)]
 
 
 def shortest_path_lhs_batch(lhs: LhsBatch, n: int = 1, device: int = -1, devices=None,
