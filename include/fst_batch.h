@@ -145,7 +145,23 @@ FstError fst_compose_frozen_shortest_path_handles_batch(FstHandle b, const FstMu
  * max_len (fst_device_compose_shortest_path) is the caller's bound on the strings'
  * lengths: it sizes workspaces and picks kernels (e.g. f32 cells when every distance
  * stays an exact integer below 2^24).  A string longer than max_len is still answered
- * exactly, by a slower tier. */
+ * exactly, by a slower tier.
+ *
+ * The stream contract of every fst_device_* entry that takes a `stream` (each comment says
+ * which of the two it is; tests/test_gpu_device_streams.py pins it on a non-blocking stream):
+ *   - inputs are read, and outputs written, in `stream` order, after the work the caller
+ *     queued on `stream` before the call: buffers that earlier work on `stream` is still
+ *     filling are valid arguments;
+ *   - an entry that is asynchronous on `stream` may return with its work still queued: later
+ *     work on `stream` sees the result, the host and other streams only after they have
+ *     waited for `stream`.  It may also wait for `stream` on some routes; callers rely on
+ *     neither;
+ *   - an entry that synchronises `stream` returns with the result complete and its host
+ *     outputs (needed, total_bytes, max_len) set;
+ *   - no other stream of the caller is waited on, the null stream included when `stream` is
+ *     non-blocking: what the call reads must be ordered before it on `stream` itself.
+ * The library's own workspaces pass from one call to the next in order, whatever streams the
+ * two calls use. */
 typedef struct {
     int32_t* status;            /* [num_strings] */
     uint32_t* path_len;         /* [num_strings] */
@@ -175,8 +191,8 @@ FstError fst_device_compose_shortest_path(FstHandle b, const uint32_t* d_labels,
  * reference's @intCast would trap), gets one input label no rhs carries (the next stage
  * reports EMPTY) and its reason in d_proj_status (the stage's status, or
  * FST_PATH_UNSUPPORTED for a non-byte label).  d_next_labels needs room for the sum of
- * path_len plus num_strings; d_next_offsets for num_strings + 1.  Synchronises `stream`
- * and returns the longest projected input in *max_len. */
+ * path_len plus num_strings; d_next_offsets for num_strings + 1.  The call
+ * synchronises `stream` and returns the longest projected input in *max_len. */
 FstError fst_device_project_output(const FstDeviceBatch* stage, uint32_t num_strings,
                                    uint32_t* d_next_labels, uint64_t* d_next_offsets,
                                    int32_t* d_proj_status, uint32_t* max_len, void* stream);
@@ -241,7 +257,7 @@ FstError fst_pipeline_lhs_batch(const FstHandle* stages, uint32_t num_stages,
  *     device-resident lattice -> text pipeline.  The arena is the caller's: items that do not
  *     fit report FST_PATH_OUTPUT_FULL and *arc_cursor ends at the arcs the batch needs; call
  *     again with that capacity.
- *   - Unlike fst_device_compose_shortest_path the call SYNCHRONISES `stream` (the engine sizes
+ *   - Unlike fst_device_compose_shortest_path the call synchronises `stream` (the engine sizes
  *     its tiers from counts it reads back); it returns with the result complete.
  *   - fst_last_launch_stats reports engine 8 / 9 as for the host entry; `launches` counts
  *     the two preparation kernels too. */
@@ -355,7 +371,7 @@ FstError fst_shortest_path_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
  * batch needs (the total states of the batch always suffice), and the result chains into
  * fst_device_project_output, fst_device_compose_shortest_path and fst_device_emit_text.  So
  * chains -> lattices (fst_device_compose_frozen) -> the caller's rescoring kernel -> 1-best ->
- * text never leaves the device.  The call SYNCHRONISES `stream`.  Engine 12; `launches` counts
+ * text never leaves the device.  The call synchronises `stream`.  Engine 12; `launches` counts
  * the two preparation kernels too. */
 FstError fst_device_shortest_path_lhs(const FstLhsBatch* d_lhs, uint32_t n,
                                       const FstBatchOptions* opts, const FstDeviceBatch* out,
@@ -415,7 +431,7 @@ FstError fst_nbest_lhs_batch(const FstLhsBatch* lhs, uint32_t n, const FstBatchO
                              FstBatchResult* out);
 
 /* Device-resident, as fst_device_shortest_path_lhs: d_lhs is a host struct of device pointers
- * with trusted extents, the prepare kernel validates the items, the call SYNCHRONISES `stream`.
+ * with trusted extents, the prepare kernel validates the items, the call synchronises `stream`.
  * `out` has room for num_fsts * n strings; the arena is the caller's, strings that do not fit
  * report FST_PATH_OUTPUT_FULL and *arc_cursor ends at what the batch needs (n * the total
  * states of the batch always suffice: a path of an acyclic item has fewer arcs than the item has
@@ -458,7 +474,7 @@ FstError fst_nbest_unique_lhs_batch(const FstLhsBatch* lhs, uint32_t n,
 
 /* Device-resident, exactly as fst_device_nbest_lhs: trusted extents, the prepare kernel (an item
  * it refuses is FST_PATH_UNSUPPORTED), the caller's arena with FST_PATH_OUTPUT_FULL and
- * *arc_cursor at what the batch needs, the call SYNCHRONISES `stream`.  The result chains into
+ * *arc_cursor at what the batch needs, the call synchronises `stream`.  The result chains into
  * fst_device_emit_text: text in, n distinct readings out.  Engine 14. */
 FstError fst_device_nbest_unique_lhs(const FstLhsBatch* d_lhs, uint32_t n,
                                      const FstBatchOptions* opts, const FstDeviceBatch* out,
@@ -467,7 +483,7 @@ FstError fst_device_nbest_unique_lhs(const FstLhsBatch* d_lhs, uint32_t n,
 /* The device-resident form, chains in and lattices out, so that a cascade never leaves the
  * device.  Every pointer in `out` is device memory on opts->device, in FstLhsBatch's layout: a
  * host-side FstLhsBatch holding those pointers goes straight into
- * fst_device_compose_shortest_path_lhs.  The call SYNCHRONISES `stream` (the tier ladder reads
+ * fst_device_compose_shortest_path_lhs.  The call synchronises `stream` (the tier ladder reads
  * counts back).  needed (host memory) receives the states and arcs the batch needs; when
  * either exceeds its capacity only `status` and `needed` are defined and nothing past a
  * capacity is written: call again with larger arrays (the pattern of fst_device_emit_text).
@@ -555,7 +571,7 @@ FstError fst_prune_lhs_batch(const FstLhsBatch* lhs, double beam, const FstBatch
  * fst_device_compose_frozen: needed receives the pruned totals; when either exceeds its capacity
  * only `status` and `needed` are defined and nothing past a capacity is written.  num_fsts == 0:
  * needed = {0, 0}, state_offsets[0] = 0 and arc_offsets[0] = 0 are written.  The call
- * SYNCHRONISES `stream`.  The result chains into every device lhs entry, so chains -> lattices ->
+ * synchronises `stream`.  The result chains into every device lhs entry, so chains -> lattices ->
  * prune -> unique n-best -> text never leaves the device.  Engine 15; `launches` counts the
  * preparation kernels too. */
 FstError fst_device_prune_lhs(const FstLhsBatch* d_lhs, double beam, const FstBatchOptions* opts,
@@ -630,7 +646,7 @@ void fst_posterior_result_free(FstPosteriorResult* r);
  * prepare kernel refuses (its ranges cannot be trusted); if state_offsets decrease anywhere every
  * item is FST_PATH_UNSUPPORTED and nothing else is written.  arc_cost lines up with d_lhs's
  * weights, so chains -> fst_device_compose_frozen -> posteriors -> the caller's own kernel ->
- * fst_device_prune_lhs or the n-best stays on the device.  The call SYNCHRONISES `stream`.
+ * fst_device_prune_lhs or the n-best stays on the device.  The call synchronises `stream`.
  * Engine 16; `launches` counts the preparation kernels too. */
 typedef struct {
     int32_t* status;      /* [num_fsts] */
@@ -712,8 +728,8 @@ FstError fst_normalize_lhs_batch(const FstHandle* stages, uint32_t num_stages,
 FstError fst_device_compile_text(const uint8_t* d_text, const uint64_t* d_offsets,
                                  uint32_t num_strings, uint32_t* d_labels, void* stream);
 /* fst_device_emit_text: a finished stage as text (d_text_offsets [num_strings + 1], d_status
- * and d_total_weight [num_strings]).  Synchronises `stream`.  *total_bytes (host) receives
- * the bytes the batch needs; no byte at or past text_capacity is written, so when
+ * and d_total_weight [num_strings]).  The call synchronises `stream`.  *total_bytes (host)
+ * receives the bytes the batch needs; no byte at or past text_capacity is written, so when
  * *total_bytes > text_capacity the text is incomplete (offsets, statuses and weights are
  * not): call again with a buffer of *total_bytes. */
 FstError fst_device_emit_text(const FstDeviceBatch* stage, uint32_t num_strings,
@@ -779,13 +795,13 @@ void fst_aligned_text_result_free(FstAlignedTextResult* r);
  * the stage's own statuses and takes any string whose entry count is not the count of its
  * path's non-epsilon olabels (offsets of another stage, or changed by a status mask of the
  * caller's) for a failed one, whose map is zeroed without an error.
- * No entry at or past `capacity` is written.
+ * No entry at or past `capacity` is written.  The call is asynchronous on `stream`.
  * fst_device_compose_alignment: the gather above.  String i's outer entries
  * [d_outer_offsets[i], d_outer_offsets[i+1]) of (d_b, d_e) index its inner symbols, whose map
  * (d_inner_begin, d_inner_end; d_inner_offsets[num_strings] entries) sits at
  * d_inner_offsets[i]; d_consumed is stage 1's.  The result goes to d_out_begin / d_out_end at
  * the outer offsets; they may be d_b and d_e themselves.  No entry at or past `capacity` is
- * read or written. */
+ * read or written.  The call is asynchronous on `stream`. */
 FstError fst_device_path_alignment(const FstDeviceBatch* stage, uint32_t num_strings,
                                    const uint64_t* d_offsets, uint32_t* d_begin,
                                    uint32_t* d_end, uint64_t capacity, uint32_t* d_consumed,
@@ -804,12 +820,18 @@ FstError fst_device_compose_alignment(uint32_t num_strings, const uint64_t* d_ou
  * offsets. */
 FstError fst_batch_result_to_aligned_text(const FstBatchResult* in, FstAlignedTextResult* out);
 
-/* Bring a frozen FST's device copy up on `device` (blob H2D + on-device SoA mirror). */
+/* Bring a frozen FST's device copy up on `device` (blob H2D + on-device SoA mirror).  Takes no
+ * stream: it works on the null stream and returns with the copy complete.  A device entry
+ * whose rhs has no copy on its device yet does the same in the middle of the call, whatever
+ * `stream` it was given. */
 FstError fst_device_prepare(FstHandle b, int32_t device);
 /* Adopt a blob that already sits in device memory on `device` (e.g. received by an
  * RCCL broadcast): validates the header, builds the SoA mirror, returns a new handle.
  * `host_copy` must hold the same bytes (used for host-side queries); may be NULL, in
- * which case the bytes are copied back from the device. */
+ * which case the bytes are copied back from the device.  Takes no stream and works on the null
+ * stream, which a non-blocking stream does not wait for: a blob that was produced
+ * asynchronously (a copy or a collective on a stream of the caller's) must be complete --
+ * that stream waited for -- before this call. */
 FstHandle fst_device_adopt_blob(const void* d_blob, uint64_t len, int32_t device,
                                 const void* host_copy);
 
